@@ -11,7 +11,8 @@ bf16 MFMA, synthetic data, random-init weights (BASELINE.json configs[1]).
 
 One "step" = one ISTrainer.batch_forward iteration with num_iters fixed to 1 (isegm/engine/trainer.py:310-491) on a
 resident batch: zero grads, forward (train mode, Dropout2d on), NFL + Dice + P2CL losses, backward, bucketed gradient
-all-reduce (N > 1), fused Adam.  Rank 0 prints ONE JSON line.
+all-reduce (N > 1), fused Adam.  Rank 0 prints ONE JSON line.  ``--dump-outputs DIR``: rank 0 also writes what the last
+timed step computed (loss terms, mask logits, gradients, weights after Adam) as DIR/<name>.npy, for comparing two builds.
 """
 import argparse
 import json
@@ -30,6 +31,9 @@ MODELS = {"vitb": dict(embed_dim=768, depth=12, num_heads=12, patch=16),
           "vith": dict(embed_dim=1280, depth=32, num_heads=16, patch=14)}
 BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA, MI355X_MICROARCH.md
 NAMES = {"vitb": "ViT-B", "vitl": "ViT-L", "vith": "ViT-H"}
+DUMP_WHOLE = 4 << 20      # --dump-outputs: an array of up to this many entries is written whole ...
+DUMP_SAMPLE = 1 << 20     # ... a larger one as this many entries at fixed, seeded positions of its flattened form
+DUMP_BYTES = 64 << 20     # at most this much in all
 
 
 def parse():
@@ -46,7 +50,12 @@ def parse():
                     help="NO GPU, NO model: only the launcher / rendezvous / bucketed reducer / JSON plumbing of an N-rank "
                          "run over gloo on the CPU with a stand-in gradient buffer (tests/test_bench_launch_cpu.py). "
                          "Prints value null: never a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -141,6 +150,29 @@ def parity_vs_oracle(ref, model_kwargs, dev):
     return out
 
 
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs DIR``: the arrays one timed step hands its caller, as float32 ``DIR/<name>.npy``, so that two builds
+    run with the same arguments (same seeded inputs) can be compared output for output.  An array of more than DUMP_WHOLE
+    entries is written as DUMP_SAMPLE entries at sorted positions drawn from a fixed seed, the positions in
+    ``DIR/<name>_index.npy`` (float64).  Returns {file name: shape} for the JSON line."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_WHOLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            out[name + "_index"] = idx.double().numpy()
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_BYTES}-byte budget")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in out.items()}
+
+
 def rehearse_launch(args, rank, world):
     """``--rehearse-launch``: the N-rank plumbing of this file WITHOUT a GPU and WITHOUT the model -- launcher, gloo
     rendezvous, parameter broadcast, the bucketed reducer fed tail-first ranges of a stand-in gradient buffer, barrier +
@@ -183,6 +215,7 @@ def rehearse_launch(args, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ok = bool(torch.all(g == world * (world + 1) / 2)) and scale == 1.0 / world
+    dumped = dump_outputs(args.dump_outputs, {"reduced_grad": g}) if args.dump_outputs and rank == 0 else None
     step(diag=True)
     dp = dp_report(red, world, "gloo", "eager (rehearsal)")
     if rank == 0:
@@ -191,7 +224,7 @@ def rehearse_launch(args, rank, world):
                           "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": args.dtype, "data": "none (launch rehearsal on the CPU: no model, no GPU)",
                           "config": {"workload": "launch rehearsal", "parallelism": f"dp{world}", "reduced_ok": ok},
-                          "dp": dp}), flush=True)
+                          "dp": dp, **({"dump_outputs": dumped} if dumped else {})}), flush=True)
     if world > 1:
         dist.destroy_process_group()
     if not ok:
@@ -412,7 +445,7 @@ def main():
             red.begin()
             eng.backward(d_inst, None, d_sim_low=d_sim)
             finish_and_step(red, opt)       # (N > 1: Adam on the reduced part while the last collectives are on the wire)
-        last["loss"] = losses["total"]
+        last["loss"], last["losses"], last["inst"] = losses["total"], losses, inst
 
     graph = [None]
     chain = [None]                     # (head graph, SegmentedBackward) of a data-parallel step
@@ -424,7 +457,7 @@ def main():
         mask = ops.dropout_mask(B, model.head.channels, keep, dev)
         inst, _ = eng.forward(image4, points, None, 0, mask, training=True, materialize_aux=False)
         losses, held["d_inst"], held["d_sim"] = vpu_step_losses(inst, None, gt, None, None, iter_weight=1.0, sim_low=eng.sim_low)
-        held["loss"] = losses["total"]
+        held["loss"], held["losses"], held["inst"] = losses["total"], losses, inst
 
     def step():
         if use_graph:
@@ -436,7 +469,7 @@ def main():
             red.begin()
             chain[0][1].replay(red.ready if red.enabled else None)
             finish_and_step(red, opt)
-            last["loss"] = held["loss"]
+            last["loss"], last["losses"], last["inst"] = held["loss"], held["losses"], held["inst"]
         else:
             step_body()
 
@@ -511,6 +544,14 @@ def main():
         dt = float(t.item())
     loss_val = float(last["loss"].item())
     value = world * B * args.steps / dt
+    # what the last timed step handed its caller (before the untimed steps below move the weights on): the loss terms, the
+    # mask logits, the gradient and the weights after Adam (the tensors a captured step keeps rewriting in place)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        ls = last["losses"]
+        dumped = dump_outputs(args.dump_outputs, {
+            "losses": torch.stack([ls["total"], ls["nfl"], ls["dice"], ls["p2cl"]]), "mask_logits": last["inst"],
+            "gradients": eng.gflat, "weights": eng.flat})
 
     roof = None
     # one extra, UNTIMED step with a HIP-event pair around every GEMM launch.  The weight-gradient side stream is
@@ -592,6 +633,8 @@ def main():
                 "roofline": roof}
         if dp is not None:
             line["dp"] = dp
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             ref = {} if (args.model == "vitb" and args.dtype == "bf16") else None
             line["cpu_baseline"] = cpu_baseline(args.cpu_batch, gpu_batch=B, keep_ref=ref)

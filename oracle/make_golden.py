@@ -1,9 +1,10 @@
-"""Generates tests/golden/*.npz by RUNNING THE REFERENCE (imported from /root/reference with the
+"""Generates tests/golden/* by RUNNING THE REFERENCE (imported from ref_import.REFERENCE_ROOT with the
 run-time stand-ins of oracle/ref_import.py) and, in the same run, checks the oracle restatement
 (oracle/vpu_oracle.py) against it.  Build-container only; the fixtures it writes are data (inputs +
 expected outputs), never reference source.
 
-    python oracle/make_golden.py            # writes tests/golden/{pue,disk,tiny,vitb,...}.npz
+    python oracle/make_golden.py            # writes tests/golden/{pue,disk,tiny,vitb,...}.npz, released_config.pth,
+                                            # shadowed_public_names.json
     python oracle/make_golden.py vitl vith  # the full-size ViT-L / ViT-H fixtures (minutes of CPU, ~20 GB of memory; not
                                             # in the default list)
 
@@ -448,6 +449,45 @@ def lrd_fixture(ref_vpu):
     print("[lrd] written", len(names), "of", len(by_id), "tensors in groups")
 
 
+def released_fixture():
+    """A checkpoint whose model config pickles the reference's own CrossEntropyLoss inside the head parameters
+    (vpu_base448_cocolvis.py:39: what released ``.pth`` files contain), written by the reference's classes as
+    ``torch.save`` writes a checkpoint.  The file holds the object's state and the dotted class path only."""
+    from isegm.model.modeling.transformer_helper.cross_entropy_loss import CrossEntropyLoss
+    assert CrossEntropyLoss.__module__ == 'isegm.model.modeling.transformer_helper.cross_entropy_loss'
+    loss = CrossEntropyLoss(use_sigmoid=False, loss_weight=1.0)
+    head = dict(in_channels=[128, 256, 512, 1024], in_index=[0, 1, 2, 3], dropout_ratio=0.1, num_classes=1,
+                loss_decode=loss, align_corners=False, upsample='x1', ed_loss=True, channels=256)
+    config = {'class': 'isegm.model.is_vpu_model.VitMultiGaussianVector_ed_Model',
+              'params': {'head_params': {'type': 'builtin', 'value': head, 'specified': True}}}
+    torch.save({'state_dict': {}, 'config': config}, os.path.join(OUT, "released_config.pth"))
+    print("[released] written")
+
+
+def public_names_fixture():
+    """For every module of the API mirror (pvpuformer_amd/isegm/**) that hides a file of the reference's isegm tree: the
+    public function and class names that file defines at its top level (names only, in file order)."""
+    import ast
+    import json
+    mirror = os.path.join(os.path.dirname(HERE), "pvpuformer_amd", "isegm")
+    table = {}
+    for dirpath, _, files in os.walk(mirror):
+        for f in files:
+            rel = os.path.relpath(os.path.join(dirpath, f), mirror)
+            ref_file = os.path.join(ref_import.REFERENCE_ROOT, "isegm", rel)
+            if not f.endswith(".py") or not os.path.isfile(ref_file):
+                continue
+            dotted = rel[:-3].replace(os.sep, ".")
+            dotted = dotted[:-len(".__init__")] if dotted.endswith(".__init__") else dotted
+            tree = ast.parse(open(ref_file).read())
+            table[dotted] = [n.name for n in tree.body
+                             if isinstance(n, (ast.FunctionDef, ast.ClassDef)) and not n.name.startswith("_")]
+    with open(os.path.join(OUT, "shadowed_public_names.json"), "w") as fh:
+        json.dump(dict(sorted(table.items())), fh, indent=1)
+        fh.write("\n")
+    print("[public_names] written", len(table), "modules")
+
+
 def scribble_fixture(ref_vpu):
     """a9: the reference's _guassinvector_scribble (is_vpu_model.py:294-352) on seeded scribbles; its debug
     ``draw_scribble`` (cv2.imwrite to a hard-coded path, ops.py:409-419) is replaced by a no-op."""
@@ -544,7 +584,12 @@ def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     ref_vpu, ref_losses = ref_import.import_reference()
-    which = sys.argv[1:] or ["pue", "tiny", "tinyh", "vitl8", "vitb", "sim", "zoom", "lrd", "scribble", "tiny_scribble"]
+    which = sys.argv[1:] or ["pue", "tiny", "tinyh", "vitl8", "vitb", "sim", "zoom", "lrd", "scribble", "tiny_scribble",
+                             "released", "public_names"]
+    if "released" in which:
+        released_fixture()
+    if "public_names" in which:
+        public_names_fixture()
     if "zoom" in which:
         zoom_fixtures()
     if "lrd" in which:
