@@ -35,8 +35,10 @@ __global__ __launch_bounds__(1024) void p2cl_kernel(const float* __restrict__ pr
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float y = ll[j];
-            const bool valid = y != -1.0f;  // ignore_label (never set by ed_mask_label, kept for fidelity)
-            if (invert) y = (y != 0.f) ? 0.f : 1.f;  // logical_not (trainer.py:330)
+            // ignore_label -1: honoured in the positive half and in override slots, where the label passes through unchanged;
+            // the inverted half is logical_not(label) (trainer.py:330), always a valid 0 / 1 -- a -1 pixel there is label 0
+            const bool valid = invert || y != -1.0f;
+            if (invert) y = (y != 0.f) ? 0.f : 1.f;
             if (!valid) y = 0.f;
             const float a = pp[j] + 1e-12f, c = 1.f - pp[j] + 1e-12f;
             const float l = -(logf(a) * y + logf(c) * (1.f - y));
@@ -280,8 +282,10 @@ __global__ __launch_bounds__(1024) void p2cl_up_kernel(const float* __restrict__
                         for (int q4 = 0; q4 < 4; ++q4) {
                             const float pr = hy * top[q4] + ly * bot[q4];
                             float y = ls[q4];
-                            const bool valid = y != -1.0f;   // ignore_label (never set by ed_mask_label, kept for fidelity)
-                            if (invert) y = (y != 0.f) ? 0.f : 1.f;   // logical_not (trainer.py:330)
+                            // ignore_label -1 in the positive half and in override slots; the inverted half is logical_not(label)
+                            // (trainer.py:330): always valid, a -1 pixel there is label 0 (as in p2cl_kernel)
+                            const bool valid = invert || y != -1.0f;
+                            if (invert) y = (y != 0.f) ? 0.f : 1.f;
                             const float a = pr + 1e-12f, c = 1.f - pr + 1e-12f;
                             const bool yb = y != 0.f;
                             const float q = yb ? a : c;
