@@ -344,6 +344,11 @@ int vpu_patch_im2col(const float* image4, const float* disks, void* cols, int32_
  * reference (is_vpu_model.py:383-419) receives what ISModel.prepare_input returned. */
 int vpu_patch_im2col_prenorm(const float* image4, const float* disks, void* cols, int32_t B, int32_t H, int32_t W, int32_t P,
                              int32_t win_tokens, int32_t dtype, void* stream);
+/* The same for any input size the reference's windowing accepts (models_vit.py:225-255): the token grid is floor(H / P) x
+ * floor(W / P), the planes keep their full size (row stride W) and only the floored g * P pixels are read, as the patch
+ * convolution does; windows of wside x wside tokens (floor(H / P) % wside == 0).  prenorm = 1: as vpu_patch_im2col_prenorm. */
+int vpu_patch_im2col_floor(const float* image4, const float* disks, void* cols, int32_t B, int32_t H, int32_t W, int32_t P,
+                           int32_t wside, int32_t prenorm, int32_t dtype, void* stream);
 /* token re-ordering between window order and raster order; dir=0: raster->window, 1: window->raster.
  * x,y [B][g*g][C] */
 int vpu_window_permute(const void* x, void* y, int32_t B, int32_t g, int32_t wg, int32_t C, int32_t dir, int32_t dtype,
@@ -355,6 +360,12 @@ int vpu_window_permute(const void* x, void* y, int32_t B, int32_t g, int32_t wg,
  * also the im2col of Conv2d(2, stride 2) (is_vpu_model.py:80). */
 int vpu_pixel_shuffle2(const void* in, void* out, const float* bias, int32_t B, int32_t h, int32_t w, int32_t C,
                        int32_t dir, int32_t dtype, void* stream);
+/* The im2col of Conv2d(2, stride 2) on a square g x g channels-last map of any g (odd g: the SimpleFPN's down_32 at a 21 /
+ * 25 / 45-token grid), torch's floored output h = g / 2.  dir=0: in [B][g][g][C] -> out [B*h*h][C*4] (column (c,di,dj), as
+ * vpu_pixel_shuffle2 dir=1), the last row and column dropped when g is odd; dir=1: the adjoint, in [B*h*h][C*4] -> out
+ * [B][g][g][C] with zeros in the dropped row and column. */
+int vpu_space_to_depth2_crop(const void* in, void* out, int32_t B, int32_t g, int32_t C, int32_t dir, int32_t dtype,
+                             void* stream);
 /* The backward of the depth-to-space of a ConvTranspose2d(2, stride 2) on channels-last maps (vpu_pixel_shuffle2 with
  * dir = 1) PLUS the bias gradient's partial sums in the same pass: part[block][c] = sum of in[..][c] over the fine pixels the
  * workgroup moved, vpu_pixel_unshuffle2_nblk(C) rows (a multiple of C / 8, <= 1024); the caller adds the rows up

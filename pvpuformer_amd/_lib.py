@@ -98,7 +98,9 @@ SIGNATURES = {
     "vpu_disk_maps": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vpu_patch_im2col": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_patch_im2col_prenorm": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vpu_patch_im2col_floor": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vpu_window_permute": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vpu_space_to_depth2_crop": [_P, _P, _I, _I, _I, _I, _I, _P],
     "vpu_pixel_shuffle2": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_pixel_shuffle2_gn_stats": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpu_groupnorm_apply": [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _I, _I, _P],

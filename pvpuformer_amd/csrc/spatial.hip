@@ -20,7 +20,10 @@ __constant__ float c_std[3] = {0.229f, 0.224f, 0.225f};
 // cols[(b*T + t_win)][ch*P*P + py*P + px], ch: 0-2 normalised rgb (ops.py:403-407), 3 prev mask, 4-5 disks
 // NORM = false: the rgb planes of img4 are normalised already (ISModel.prepare_input ran on the caller's side: the public
 // backbone_forward, is_vpu_model.py:383-419)
-template <typename T, bool NORM = true>
+// The token grid is floor(H / P) x floor(W / P) and rows are addressed with the plane's own width W, so an input whose side
+// is not a multiple of P is covered up to its floored g * P pixels, as the patch convolution does (vpu_patch_im2col_floor).
+// VEC = false: the element-wise form only (rows of a plane whose width is not a multiple of 4 are not 16-byte aligned).
+template <typename T, bool NORM = true, bool VEC = true>
 __global__ __launch_bounds__(256) void patch_im2col_kernel(const float* __restrict__ img4,
                                                            const float* __restrict__ disks, T* __restrict__ cols,
                                                            int B, int H, int W, int P, int wg) {
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256) void patch_im2col_kernel(const float* __restri
         const int win = tw / (wg * wg), inner = tw % (wg * wg);
         const int ty = (win / nwx) * wg + inner / wg, tx = (win % nwx) * wg + inner % wg;
         float o[8];
-        if ((P & 7) == 0) {
+        if (VEC && (P & 7) == 0) {
             // P % 8 == 0 (patch 16): the 8 columns of a chunk are 8 consecutive pixels of one patch row of one channel --
             // one set of index divisions and two 16-byte loads per thread (the element-wise form below: six divisions and
             // a 4-byte load per element, 53 us at ViT-B bs 12)
@@ -142,6 +145,55 @@ __global__ __launch_bounds__(256) void pixel_shuffle2_kernel(const T* __restrict
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) store8(dst + coarse + g * 8, v[g]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------ 2x2 space-to-depth on an odd grid
+// Conv2d(C, C', 2, stride=2) on a g x g map floors its output to h = g / 2: with g odd the last row and column of the map
+// are never read.  dir 0: x [B][g][g][C] -> s2d [B*h*h][C*4] (column c*4 + di*2 + dj, vpu_pixel_shuffle2's inverse
+// layout); dir 1, the adjoint: s2d -> x, ZEROS in the dropped row and column.  One thread moves 8 channels of the 4
+// sub-pixels of one 2 x 2 cell; dir 1 walks (g + 1) / 2 cells per side, the border cells write their in-range pixels as 0.
+template <typename T>
+__global__ __launch_bounds__(256) void space_to_depth2_crop_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int g,
+                                                                   int C, int dir) {
+    const int chunks = C / 8, h = g / 2, hc = dir == 0 ? h : (g + 1) / 2;
+    const int64_t total = (int64_t)B * hc * hc * chunks;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int ck = (int)(i % chunks);
+        const int64_t cell = i / chunks;
+        const int x = (int)(cell % hc), y = (int)((cell / hc) % hc);
+        const int64_t b = cell / ((int64_t)hc * hc);
+        const int64_t fine0 = ((b * g + 2 * y) * g + 2 * x) * C + ck * 8;       // sub-pixel (0, 0)
+        if (y >= h || x >= h) {                                                 // (dir 1 only: the dropped border)
+            const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dd = 0; dd < 4; ++dd)
+                if (2 * y + (dd >> 1) < g && 2 * x + (dd & 1) < g) store8(dst + fine0 + ((int64_t)(dd >> 1) * g + (dd & 1)) * C, z);
+            continue;
+        }
+        const int64_t coarse = ((b * h + y) * h + x) * (C * 4) + (int64_t)ck * 32;
+        float v[4][8];   // [column group of 8][k]: coarse element q*8+k = channel (q*8+k)/4, sub-pixel (q*8+k)%4
+        if (dir == 0) {
+#pragma unroll
+            for (int dd = 0; dd < 4; ++dd) {
+                float o[8];
+                load8(src + fine0 + ((int64_t)(dd >> 1) * g + (dd & 1)) * C, o);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[(j * 4 + dd) >> 3][(j * 4 + dd) & 7] = o[j];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) store8(dst + coarse + q * 8, v[q]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) load8(src + coarse + q * 8, v[q]);
+#pragma unroll
+            for (int dd = 0; dd < 4; ++dd) {
+                float o[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = v[(j * 4 + dd) >> 3][(j * 4 + dd) & 7];
+                store8(dst + fine0 + ((int64_t)(dd >> 1) * g + (dd & 1)) * C, o);
+            }
         }
     }
 }
@@ -1497,6 +1549,36 @@ extern "C" int vpu_patch_im2col_prenorm(const float* image4, const float* disks,
     DISPATCH_T(dtype, (patch_im2col_kernel<T, false><<<vpu_grid_for(total, 256, 16384), 256, 0, ST>>>(
         image4, disks, (T*)cols, B, H, W, P, win_tokens));)
     return vpu_check_launch("vpu_patch_im2col_prenorm");
+}
+extern "C" int vpu_patch_im2col_floor(const float* image4, const float* disks, void* cols, int32_t B, int32_t H, int32_t W,
+                                      int32_t P, int32_t wside, int32_t prenorm, int32_t dtype, void* stream) {
+    vpu_clear_stale_error();
+    if (!image4 || !disks || !cols || B < 1 || P < 1 || wside < 1 || H < P || W < P || (H / P) % wside || (W / P) % wside) {
+        vpu_set_error("patch_im2col_floor: H, W >= P, floor(H / P) and floor(W / P) multiples of the window side, non-null pointers");
+        return VPU_ERR_ARG;
+    }
+    const int64_t total = (int64_t)B * (H / P) * (W / P) * (2 * ((3 * P * P + 7) / 8));
+    const int grid = vpu_grid_for(total, 256, 16384);
+    const bool vec = W % 4 == 0;
+    DISPATCH_T(dtype,
+               if (prenorm && vec) patch_im2col_kernel<T, false, true><<<grid, 256, 0, ST>>>(image4, disks, (T*)cols, B, H, W, P, wside);
+               else if (prenorm) patch_im2col_kernel<T, false, false><<<grid, 256, 0, ST>>>(image4, disks, (T*)cols, B, H, W, P, wside);
+               else if (vec) patch_im2col_kernel<T, true, true><<<grid, 256, 0, ST>>>(image4, disks, (T*)cols, B, H, W, P, wside);
+               else patch_im2col_kernel<T, true, false><<<grid, 256, 0, ST>>>(image4, disks, (T*)cols, B, H, W, P, wside);)
+    return vpu_check_launch("vpu_patch_im2col_floor");
+}
+extern "C" int vpu_space_to_depth2_crop(const void* in, void* out, int32_t B, int32_t g, int32_t C, int32_t dir, int32_t dtype,
+                                        void* stream) {
+    vpu_clear_stale_error();
+    if (!in || !out || B < 1 || g < 2 || C < 8 || C % 8 || (dir != 0 && dir != 1)) {
+        vpu_set_error("space_to_depth2_crop: g >= 2, C % 8 == 0, dir 0 / 1, non-null pointers");
+        return VPU_ERR_ARG;
+    }
+    const int hc = dir == 0 ? g / 2 : (g + 1) / 2;
+    const int64_t total = (int64_t)B * hc * hc * (C / 8);
+    DISPATCH_T(dtype, space_to_depth2_crop_kernel<T><<<vpu_grid_for(total, 256, 16384), 256, 0, ST>>>((const T*)in, (T*)out, B, g,
+                                                                                                     C, dir);)
+    return vpu_check_launch("vpu_space_to_depth2_crop");
 }
 extern "C" int vpu_window_permute(const void* x, void* y, int32_t B, int32_t g, int32_t wg, int32_t C, int32_t dir,
                                   int32_t dtype, void* stream) {

@@ -90,6 +90,29 @@ def pos2d_table(d_model, height, width):
     return pe.reshape(d_model, height * width).t().contiguous()
 
 
+def window_geometry(S, P):
+    """(g, nwin, wside) of an S x S input with P x P patches, as the reference's ``patchify`` derives them
+    (models_vit.py:225-255): the patch convolution floors the grid to g = S // P tokens per side, the windows are laid out
+    for 224-pixel pretraining, nwin = g // (224 // P) per side, each wside = g // nwin tokens wide.  A size is legal when
+    g >= 224 // P and g % nwin == 0 (the reference's view() needs it); anything else raises ValueError."""
+    S, P = int(S), int(P)
+    wg = 224 // P
+    g = S // P if P > 0 else 0
+    if P < 1 or wg < 1 or g < wg:
+        raise ValueError(f"input side {S} with patch {P}: the token grid S // P = {g} must hold at least one "
+                         f"{wg}-token window (S >= {wg * P})")
+    nwin = g // wg
+    if g % nwin:
+        raise ValueError(f"input side {S} with patch {P}: the token grid g = S // P = {g} must split into nwin = g // {wg} = "
+                         f"{nwin} equal windows per side (g % nwin == 0), as the reference's patchify requires")
+    return g, nwin, g // nwin
+
+
+def check_square(H, W):
+    if H != W:
+        raise ValueError(f"input {H}x{W}: only square inputs are supported (the reference's neck takes h = w = sqrt(HW))")
+
+
 class Engine:
     def __init__(self, cfg, dtype="bf16", device="cuda"):
         self.cfg = dict(cfg)
@@ -98,10 +121,10 @@ class Engine:
         self.dev = torch.device(device)
         c = self.cfg
         self.D, self.P, self.img = c["embed_dim"], c["patch"], c["img"]
-        self.g = self.img // self.P
+        # the trained token grid and its window side (window_geometry: the reference's patchify); forward derives both
+        # from the input it is given
+        self.g, _, self.wside = window_geometry(self.img, self.P)
         self.NT = self.g * self.g
-        self.wg = 224 // self.P
-        self.nw = self.g // self.wg
         self.heads = c["num_heads"]
         self.depth = c["depth"]
         self.group = 6 if self.depth == 12 else self.depth // 4
@@ -256,8 +279,8 @@ class Engine:
             ops.cast2d(self.Pm("neck.ffn_layer.lin1.weight"), self.E, self.w_lin1p, self.Epad, 2048, self.E, self.Epad)
             tmp = torch.empty(self.NT, D, device=self.dev, dtype=self.td)
             ops.cast2d((self.flat, po + D), D, tmp, D, self.NT, D)
-            ops.window_permute(tmp, self.pos_win, 1, self.g, self.wg, D, to_raster=False)
-            self._pos_cache = {self.g: self.pos_win}
+            ops.window_permute(tmp, self.pos_win, 1, self.g, self.wside, D, to_raster=False)
+            self._pos_cache = {(self.g, self.wside): self.pos_win}
             self.shadow_valid = True
             return
         # the derived operands in ONE launch (round 5: vpu_cast2d_batched; five launches before): the two patch embeddings side
@@ -270,9 +293,9 @@ class Engine:
                  ld_src=D, ld_dst=D, rows=1, cols=D),
             dict(src=self.Pm("neck.ffn_layer.lin1.weight"), dst=self.w_lin1p, ld_src=self.E, ld_dst=self.Epad, rows=2048, cols=self.E,
                  cols_pad=self.Epad),
-            dict(src=(self.flat, po + D), dst=self.pos_win, ld_src=D, ld_dst=D, rows=self.NT, cols=D, perm=(self.g, self.wg)),
+            dict(src=(self.flat, po + D), dst=self.pos_win, ld_src=D, ld_dst=D, rows=self.NT, cols=D, perm=(self.g, self.wside)),
         ])
-        self._pos_cache = {self.g: self.pos_win}      # other grids are re-derived from the new weights on demand
+        self._pos_cache = {(self.g, self.wside): self.pos_win}      # other grids are re-derived from the new weights on demand
         self.shadow_valid = True
 
     def _regrid_adjoint(self, g):
@@ -289,13 +312,13 @@ class Engine:
             self._regrid_cache[g] = Rt
         return Rt
 
-    def _pos_for(self, g):
+    def _pos_for(self, g, wside):
         """Window-ordered position embedding for a g x g token grid.  The trained grid is used as it is; any other one
         (evaluation at another input size: scripts/evaluate_vpumodel.py:125 -> pos_embed.py:99-128, e.g. DAVIS at 672^2 =
         42 x 42 tokens, 9 windows) is the bicubic re-gridding of the trained embedding, exactly the tensor the reference
         installs with interpolate_pos_embed_inference -- computed once per grid and weight state (torch's bicubic
-        interpolate: load-time plumbing, not the hot path)."""
-        pw = self._pos_cache.get(g)
+        interpolate: load-time plumbing, not the hot path).  Cached per (grid, window side)."""
+        pw = self._pos_cache.get((g, wside))
         if pw is None:
             import torch.nn.functional as F
             D, g0 = self.D, self.g
@@ -304,8 +327,8 @@ class Engine:
             new = F.interpolate(grid, size=(g, g), mode="bicubic", align_corners=False).permute(0, 2, 3, 1)
             tmp = new.reshape(g * g, D).to(self.td).contiguous()
             pw = torch.empty(g * g, D, device=self.dev, dtype=self.td)
-            ops.window_permute(tmp, pw, 1, g, self.wg, D, to_raster=False)
-            self._pos_cache[g] = pw
+            ops.window_permute(tmp, pw, 1, g, wside, D, to_raster=False)
+            self._pos_cache[(g, wside)] = pw
         return pw
 
     def _kpe_for(self, g):
@@ -930,11 +953,17 @@ class Engine:
             self.tape.append(bwd)
         return y
 
-    def conv_s2(self, x, prefix, B, h, w, Cin, Cout):
-        """Conv2d(Cin, Cout, 2, stride=2) on a channels-last [B, 2h, 2w, Cin] map = space-to-depth + GEMM."""
+    def conv_s2(self, x, prefix, B, h, w, Cin, Cout, g=None):
+        """Conv2d(Cin, Cout, 2, stride=2) on a channels-last [B, 2h, 2w, Cin] map = space-to-depth + GEMM.  ``g`` odd: the map
+        is [B, g, g, Cin] with h = w = g // 2, its last row and column are dropped (vpu_space_to_depth2_crop) as Conv2d does."""
+        odd = g is not None and g % 2 == 1
+        assert g is None or (h == w == g // 2)
         M = B * h * w
         s2d = self._new(M, 4 * Cin)
-        ops.pixel_shuffle2(x.t, s2d, None, B, h, w, Cin, inverse=True)
+        if odd:
+            ops.space_to_depth2_crop(x.t, s2d, B, g, Cin)
+        else:
+            ops.pixel_shuffle2(x.t, s2d, None, B, h, w, Cin, inverse=True)
         y = Var(self._new(M, Cout))
         ops.gemm(s2d, self.W(prefix + ".weight"), y.t, M, Cout, 4 * Cin, 4 * Cin, 4 * Cin, Cout, self.dt,
                  flags=EPI_BIAS, bias=self.Pm(prefix + ".bias"))
@@ -946,8 +975,12 @@ class Engine:
                 ds = self._new(M, 4 * Cin)
                 ops.gemm(y.g, self.W(prefix + ".weight"), ds, M, 4 * Cin, Cout, Cout, 4 * Cin, 4 * Cin, self.dt,
                          transB=True)
-                dx = self._new(B * 4 * h * w, Cin)
-                ops.pixel_shuffle2(ds, dx, None, B, h, w, Cin)
+                if odd:
+                    dx = self._new(B * g * g, Cin)
+                    ops.space_to_depth2_crop(ds, dx, B, g, Cin, inverse=True)
+                else:
+                    dx = self._new(B * 4 * h * w, Cin)
+                    ops.pixel_shuffle2(ds, dx, None, B, h, w, Cin)
                 self.acc(x, dx, take=True)
             self.tape.append(bwd)
         return y
@@ -974,11 +1007,12 @@ class Engine:
         D, P, heads = self.D, self.P, self.heads
         # the token grid follows the INPUT (the prompt vectors keep the constructor's image size, as in the reference:
         # is_vpu_model.py:189-230 builds them from self.image_size)
-        if H != W_ or H % (P * self.wg) != 0:
-            raise ValueError(f"input {H}x{W_}: square inputs whose side is a multiple of the {P * self.wg}-pixel window")
-        g = H // P
-        NT, nw_side = g * g, g // self.wg
-        pos_win, kpe_tab = self._pos_for(g), self._kpe_for(g)
+        # (window_geometry: any square size the reference's patchify accepts; the grid is floored when H % P != 0 and the
+        # last H % P pixel rows / columns are read by nothing but the final upsample's output shape)
+        check_square(H, W_)
+        g, nw_side, wside = window_geometry(H, P)
+        NT = g * g
+        pos_win, kpe_tab = self._pos_for(g, wside), self._kpe_for(g)
         M = B * NT
         self._token_rows = M          # the reduction length of the ViT blocks' weight gradients (the packed queue)
         n = points.shape[1] // 2
@@ -1067,7 +1101,10 @@ class Engine:
             taps["disks"] = disks
         KP = 2 * self.k3p
         cols = self._new(M, KP)
-        ops.patch_im2col(image4, disks, cols, B, H, W_, P, self.wg, prenorm=prenorm)
+        if H % P == 0:
+            ops.patch_im2col(image4, disks, cols, B, H, W_, P, wside, prenorm=prenorm)
+        else:
+            ops.patch_im2col_floor(image4, disks, cols, B, H, W_, P, wside, prenorm=prenorm)
         x = Var(self._new(M, D))
         ops.gemm(cols, self.w_patch, x.t, M, D, KP, KP, KP, D, self.dt,
                  flags=EPI_BIAS | EPI_RESID, bias=self.b_patch, resid=pos_win, ldr=D, resid_period=NT)
@@ -1084,7 +1121,7 @@ class Engine:
                 s = self._new(NT * D, dtype=torch.float32)
                 ops.colsum(x0.g, NT * D, s, None, B, NT * D, beta=0.0)   # rows = B <= 64: single-pass kernel
                 r = self._new(NT * D, dtype=torch.float32)
-                ops.window_permute(s, r, 1, g, self.wg, D, to_raster=True)
+                ops.window_permute(s, r, 1, g, wside, D, to_raster=True)
                 gp = (self.gflat, self.names["backbone.pos_embed"][0] + D)
                 if g == self.g:
                     ops.add4(gp, r, None, None, gp, NT * D)
@@ -1120,7 +1157,7 @@ class Engine:
             h2 = self.layernorm(x1, p + "norm2", M, D, 1e-6)
             x = self.mlp(h2, p + "mlp.fc1", p + "mlp.fc2", M, D, D * c["mlp_ratio"], D, "gelu", resid=x1)
         xr = Var(self._new(M, D))
-        ops.window_permute(x.t, xr.t, B, g, self.wg, D, to_raster=True)
+        ops.window_permute(x.t, xr.t, B, g, wside, D, to_raster=True)
         if training:
             xw = x
 
@@ -1128,7 +1165,7 @@ class Engine:
                 if xr.g is None:
                     return
                 gw = torch.empty_like(xr.g)
-                ops.window_permute(xr.g, gw, B, g, self.wg, D, to_raster=False)
+                ops.window_permute(xr.g, gw, B, g, wside, D, to_raster=False)
                 self.acc(xw, gw, take=True)
             self.tape.append(bwd_perm)
         if taps is not None:
@@ -1324,11 +1361,12 @@ class Engine:
         a = self.linear(maps[2], "neck.down_16.0.weight", "neck.down_16.0.bias", M, o[2], D)
         d16 = self.groupnorm(a, "neck.down_16.1", B, NT, o[2], True)
         c32 = max(o[3], D * 2)
-        a = self.conv_s2(maps[3], "neck.down_32.0", B, g // 2, g // 2, D, c32)
-        a = self.groupnorm(a, "neck.down_32.1", B, NT // 4, c32, False)
-        a = self.linear(a, "neck.down_32.2.weight", "neck.down_32.2.bias", B * NT // 4, o[3], c32)
-        d32 = self.groupnorm(a, "neck.down_32.3", B, NT // 4, o[3], True)
-        feats = [(d4, 4 * g), (d8, 2 * g), (d16, g), (d32, g // 2)]
+        h32 = g // 2                  # Conv2d(2, stride 2) floors: an odd grid loses its last row and column
+        a = self.conv_s2(maps[3], "neck.down_32.0", B, h32, h32, D, c32, g=g)
+        a = self.groupnorm(a, "neck.down_32.1", B, h32 * h32, c32, False)
+        a = self.linear(a, "neck.down_32.2.weight", "neck.down_32.2.bias", B * h32 * h32, o[3], c32)
+        d32 = self.groupnorm(a, "neck.down_32.3", B, h32 * h32, o[3], True)
+        feats = [(d4, 4 * g), (d8, 2 * g), (d16, g), (d32, h32)]
         if taps is not None:
             for i, (f, s) in enumerate(feats):
                 taps[f"fpn{i}"] = f.t

@@ -446,6 +446,19 @@ def patch_im2col(image4, disks, cols, B, H, W, P, win_tokens, prenorm=False):
               win_tokens, code_of(cols), _stream())
 
 
+def patch_im2col_floor(image4, disks, cols, B, H, W, P, wside, prenorm=False):
+    """patch_im2col for any legal input size: a floor(H / P) x floor(W / P) token grid in windows of ``wside`` tokens per
+    side, read from the full-size planes (vpu_patch_im2col_floor)."""
+    _lib.call("vpu_patch_im2col_floor", ptr(image4), ptr(disks), ptr(cols), B, H, W, P, wside, int(bool(prenorm)), code_of(cols),
+              _stream())
+
+
+def space_to_depth2_crop(src, dst, B, g, Cdim, inverse=False):
+    """Conv2d(2, stride 2) im2col of a g x g channels-last map, any g (the last row / column dropped when g is odd);
+    ``inverse``: the adjoint, zeros in the dropped row / column."""
+    _lib.call("vpu_space_to_depth2_crop", ptr(src), ptr(dst), B, g, Cdim, 1 if inverse else 0, code_of(src), _stream())
+
+
 def window_permute(x, y, B, g, wg, Cdim, to_raster):
     _lib.call("vpu_window_permute", ptr(x), ptr(y), B, g, wg, Cdim, 1 if to_raster else 0, code_of(x), _stream())
 
