@@ -316,6 +316,38 @@ int vpu_error_masks(const uint8_t* pred, const uint8_t* gt, const uint8_t* valid
                     void* stream);
 int vpu_masked_argmax(const float* dist, const uint8_t* keep, uint64_t* out, int32_t planes, int32_t H, int32_t W,
                       void* stream);
+/* Batched NoBRS evaluation (evalbatch.hip; pvpuformer_amd/isegm/inference/batched.py): K objects of different sizes step
+ * through the click loop in lock-step.  Each launch reads a DEVICE array of n per-object descriptors:
+ *   image fp32 [3][H][W], prev fp32 [H][W] (previous prediction; unused with 3 channels), canvas fp32 [H][W] (16-byte
+ *   aligned), mask / gt (== 1) / valid (!= ignore) / keep (not clicked) uint8 [H][W] (4-byte aligned), the inclusive roi
+ *   (r0, r1, c0, c1) inside [H][W], src = the object's slot in the network batch, clear_at = pixel index set to 0 in keep
+ *   before the click keys (-1: none), out = int64 [6]: the two click keys, then int32 [8] statistics. */
+typedef struct vpu_eval_obj {
+    const float* image;
+    const float* prev;
+    float* canvas;
+    uint8_t* mask;
+    const uint8_t* gt;
+    const uint8_t* valid;
+    uint8_t* keep;
+    int64_t* out;
+    int32_t H, W, r0, r1, c0, c1, src, clear_at;
+} vpu_eval_obj;
+/* out fp32 [2n or n][channels][S_h][S_w] (16-byte aligned, S_w % 4 == 0): slot src = crop_resize(cat(image, prev), roi,
+ * (S_h, S_w)) (align_corners=True, vpu_upsample_ac_fwd's per-pixel formula; a crop of the output size is copied); flip != 0:
+ * slot n + src = its mirror image (AddHorizontalFlip on the batch). */
+int vpu_roi_resize_batched(const vpu_eval_obj* objs, int32_t n, float* out, int32_t S_h, int32_t S_w, int32_t flip,
+                           int32_t channels, void* stream);
+/* ZoomIn.inv_transform of probs fp32 [*][S_h][S_w] (map src) into each object's canvas: resized to the roi's size and pasted
+ * into zeros; mask = canvas > pred_thr; int32 statistics at out + 2: {|mask & gt & valid|, |(mask | gt) & valid|, then
+ * vpu_mask_bbox's {count, rmin, rmax, cmin, cmax} of canvas > box_thr without clicks}.  max_hw >= every H * W. */
+int vpu_roi_paste_batched(const vpu_eval_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w, float pred_thr,
+                          float box_thr, int32_t max_hw, void* stream);
+/* The Clicker's two keys (false negatives, false positives; vpu_masked_argmax packing, index r * W + c of the object's own
+ * map) of mask against gt inside valid, exact EDT with zero_border, arg-max over keep -> out[0], out[1].  Scratch: err
+ * uint8, scratch int32 and dist fp32, each [2n][Hm][Wm], Hm >= every H, Wm >= every W, Wm % 4 == 0; max_hw >= every H * W. */
+int vpu_click_keys_batched(const vpu_eval_obj* objs, int32_t n, uint8_t* err, int32_t* scratch, float* dist, int32_t Hm,
+                           int32_t Wm, int32_t max_hw, void* stream);
 /* 8-connected components of B masks [B][H][W]: roots[i] = smallest linear index (within the whole [B][H][W] array) of the
  * component of non-zero pixel i, -1 on zero pixels.  Sorted by root, the components are in the raster order of their first
  * pixel -- the label order of the reference's skimage.measure.label(connectivity=2) in max_connected_regions

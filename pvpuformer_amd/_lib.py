@@ -51,6 +51,14 @@ class CastJob(C.Structure):
                 ("perm_g", C.c_int32), ("perm_wg", C.c_int32)]
 
 
+class EvalObj(C.Structure):
+    """vpu_eval_obj (include/vpu_hip.h): one object of the batched NoBRS kernels."""
+    _fields_ = [("image", C.c_void_p), ("prev", C.c_void_p), ("canvas", C.c_void_p), ("mask", C.c_void_p),
+                ("gt", C.c_void_p), ("valid", C.c_void_p), ("keep", C.c_void_p), ("out", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("r0", C.c_int32), ("r1", C.c_int32), ("c0", C.c_int32),
+                ("c1", C.c_int32), ("src", C.c_int32), ("clear_at", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -95,6 +103,9 @@ SIGNATURES = {
     "vpu_mask_bbox": [_P, _F, _P, _I, _P, _I, _I, _I, _P],
     "vpu_masked_argmax": [_P, _P, _P, _I, _I, _I, _P],
     "vpu_error_masks": [_P, _P, _P, _P, _I, _I, _P],
+    "vpu_roi_resize_batched": [_P, _I, _P, _I, _I, _I, _I, _P],
+    "vpu_roi_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _P],
+    "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_disk_maps": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vpu_patch_im2col": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_patch_im2col_prenorm": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -1,0 +1,252 @@
+// Batched NoBRS evaluation (pvpuformer_amd/isegm/inference/batched.py): K objects of different images and sizes step
+// through the click loop together.  Every kernel reads a device array of per-object descriptors (vpu_eval_obj,
+// include/vpu_hip.h), so that one launch covers all of them whatever their sizes.  All passes are bandwidth-bound
+// streams over the objects' canvases: 4 pixels per thread (16-byte fp32 / 4-byte uint8 accesses), block-level reduction,
+// one atomic per workgroup and counter.  Kernels neither allocate nor synchronise (hipGraph-capturable).
+#include "vpu_common.h"
+#include "interp_ac.h"
+#include "../../include/vpu_hip.h"
+
+#define ST reinterpret_cast<hipStream_t>(stream)
+
+namespace {
+
+// -------------------------------------------------------------------------------------------------------------------
+// (1) network input: crop_resize(cat(image, prev), roi, (S_h, S_w)) of object b into batch slot d.src and, with flip, its
+//     mirror image into slot n + d.src (AddHorizontalFlip on a batch: [straight..., mirrored...]).  A crop already of the
+//     output size is copied, as crop_resize does (it clones instead of resizing).  4 output pixels per thread along a row.
+__global__ __launch_bounds__(256) void roi_resize_kernel(const vpu_eval_obj* __restrict__ objs, int n, float* __restrict__ out,
+                                                         int S_h, int S_w, int flip, int channels) {
+    const vpu_eval_obj& d = objs[blockIdx.y];
+    const int h = d.r1 - d.r0 + 1, w = d.c1 - d.c0 + 1;
+    const bool copy = h == S_h && w == S_w;
+    const float sh = ac_scale(h, S_h), sw = ac_scale(w, S_w);
+    const int quads = S_w / 4;                                  // (host: S_w % 4 == 0)
+    const int64_t plane = (int64_t)S_h * S_w;
+    const int64_t total = (int64_t)channels * S_h * quads;
+    float* straight = out + (int64_t)d.src * channels * plane;
+    float* mirrored = out + ((int64_t)n + d.src) * channels * plane;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+        const int X = (int)(q % quads) * 4;
+        const int Y = (int)((q / quads) % S_h);
+        const int c = (int)(q / ((int64_t)quads * S_h));
+        const float* src = (c < 3 ? d.image + (int64_t)c * d.H * d.W : d.prev) + (int64_t)d.r0 * d.W + d.c0;
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            v[u] = copy ? src[(int64_t)Y * d.W + X + u] : ac_sample(src, d.W, h, w, sh, sw, Y, X + u);
+        const int64_t o = (int64_t)c * plane + (int64_t)Y * S_w;
+        *reinterpret_cast<float4*>(straight + o + X) = make_float4(v[0], v[1], v[2], v[3]);
+        if (flip) *reinterpret_cast<float4*>(mirrored + o + (S_w - 4 - X)) = make_float4(v[3], v[2], v[1], v[0]);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// (2) ZoomIn.inv_transform + the per-click bookkeeping in one pass over each object's [H, W] canvas: the [S_h, S_w]
+//     probability map d.src resized to the roi's (h, w) and pasted into zeros, the mask canvas > pred_thr, the IoU counts
+//     of that mask against gt inside valid (utils.get_iou), and the box of canvas > box_thr (vpu_mask_bbox without the
+//     clicks: the host joins them, it knows the click of the next step only after this read-back).
+//     stats (int32 view of d.out + 2): {intersection, union, count, rmin, rmax, cmin, cmax, -}, set by paste_init_kernel.
+struct PasteAcc {
+    int inter = 0, uni = 0, cnt = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
+};
+
+__device__ __forceinline__ void paste_pixel(const vpu_eval_obj& d, const float* __restrict__ src, int S_h, int S_w, bool copy,
+                                            float sh, float sw, int h, int w, float pred_thr, float box_thr, int64_t i,
+                                            uint8_t g, uint8_t valid, float& v, uint8_t& m, PasteAcc& a) {
+    const int r = (int)(i / d.W), c = (int)(i - (int64_t)r * d.W);
+    v = 0.f;
+    if (r >= d.r0 && r <= d.r1 && c >= d.c0 && c <= d.c1)
+        v = copy ? src[(int64_t)(r - d.r0) * S_w + (c - d.c0)] : ac_sample(src, S_w, S_h, S_w, sh, sw, r - d.r0, c - d.c0);
+    m = v > pred_thr ? 1 : 0;
+    if (valid) {
+        a.inter += (m && g) ? 1 : 0;
+        a.uni += (m || g) ? 1 : 0;
+    }
+    if (v > box_thr) {
+        ++a.cnt;
+        a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
+    }
+}
+
+__global__ void paste_init_kernel(const vpu_eval_obj* __restrict__ objs, int n) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    const vpu_eval_obj& d = objs[b];
+    int* s = reinterpret_cast<int*>(d.out + 2);
+    s[0] = 0; s[1] = 0; s[2] = 0; s[3] = d.H; s[4] = -1; s[5] = d.W; s[6] = -1; s[7] = 0;
+}
+
+__global__ __launch_bounds__(256) void roi_paste_kernel(const vpu_eval_obj* __restrict__ objs, const float* __restrict__ probs,
+                                                        int S_h, int S_w, float pred_thr, float box_thr) {
+    const vpu_eval_obj& d = objs[blockIdx.y];
+    const int h = d.r1 - d.r0 + 1, w = d.c1 - d.c0 + 1;
+    const bool copy = h == S_h && w == S_w;
+    // the map is resized from (S_h, S_w) to the roi's (h, w): steps of that resize
+    const float sh = ac_scale(S_h, h), sw = ac_scale(S_w, w);
+    const float* src = probs + (int64_t)d.src * S_h * S_w;
+    const int64_t HW = (int64_t)d.H * d.W, quads = HW / 4;
+    PasteAcc a;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
+        const uchar4 g = *reinterpret_cast<const uchar4*>(d.gt + 4 * q);
+        const uchar4 vl = *reinterpret_cast<const uchar4*>(d.valid + 4 * q);
+        float v[4]; uint8_t m[4];
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 0, g.x, vl.x, v[0], m[0], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 1, g.y, vl.y, v[1], m[1], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 2, g.z, vl.z, v[2], m[2], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 3, g.w, vl.w, v[3], m[3], a);
+        *reinterpret_cast<float4*>(d.canvas + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<uchar4*>(d.mask + 4 * q) = make_uchar4(m[0], m[1], m[2], m[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(HW - 4 * quads)) {        // the last HW % 4 pixels
+        const int64_t i = 4 * quads + threadIdx.x;
+        float v; uint8_t m;
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, i, d.gt[i], d.valid[i], v, m, a);
+        d.canvas[i] = v;
+        d.mask[i] = m;
+    }
+    // block reduction: wave shuffles, then the four waves' partials through LDS; one atomic per block and counter
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.inter += __shfl_xor(a.inter, o, 64); a.uni += __shfl_xor(a.uni, o, 64); a.cnt += __shfl_xor(a.cnt, o, 64);
+        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
+        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
+    }
+    __shared__ int red[4][7];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = a.inter; red[wave][1] = a.uni; red[wave][2] = a.cnt;
+        red[wave][3] = a.r0; red[wave][4] = a.r1; red[wave][5] = a.c0; red[wave][6] = a.c1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            red[0][0] += red[k][0]; red[0][1] += red[k][1]; red[0][2] += red[k][2];
+            red[0][3] = min(red[0][3], red[k][3]); red[0][4] = max(red[0][4], red[k][4]);
+            red[0][5] = min(red[0][5], red[k][5]); red[0][6] = max(red[0][6], red[k][6]);
+        }
+        int* s = reinterpret_cast<int*>(d.out + 2);
+        if (red[0][0]) atomicAdd(s + 0, red[0][0]);
+        if (red[0][1]) atomicAdd(s + 1, red[0][1]);
+        if (red[0][2]) {
+            atomicAdd(s + 2, red[0][2]);
+            atomicMin(s + 3, red[0][3]); atomicMax(s + 4, red[0][4]); atomicMin(s + 5, red[0][5]); atomicMax(s + 6, red[0][6]);
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// (3) oracle click keys (Clicker._deepest_errors_device) of every object in one pass per stage.
+//     The error masks of object b go to planes 2b (false negatives) and 2b + 1 (false positives) of a [2n][Hm][Wm]
+//     canvas, zero beyond the object's own [H, W]; one vpu_edt (zero_border) over all planes; then the masked arg-max
+//     over the object's own region with its own not-clicked map and its own raster index r * W + c.
+//     Why the zero padding does not change a distance inside [0, H) x [0, W): the reference pads each error mask with a
+//     1-pixel zero frame, i.e. rows -1 and H, columns -1 and W.  The padded canvas has those zeros too (its row H /
+//     column W, or vpu_edt's own frame when H == Hm / W == Wm), plus further zeros farther out.  Every such extra zero q
+//     lies outside the box [-1, H] x [-1, W]; clamping q's coordinates into the box gives a frame pixel that is at least
+//     as close to any pixel inside (projection onto a box shortens every distance to points in it).  So the nearest
+//     zero is at the same distance with or without the extra zeros.
+__global__ __launch_bounds__(256) void click_err_kernel(const vpu_eval_obj* __restrict__ objs, uint8_t* __restrict__ err,
+                                                        int Hm, int Wm) {
+    const vpu_eval_obj& d = objs[blockIdx.y];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (d.clear_at >= 0) d.keep[d.clear_at] = 0;       // the click just made (Clicker.add_click marks it)
+        d.out[0] = 0; d.out[1] = 0;                        // keys: max-reduced below
+    }
+    const int64_t plane = (int64_t)Hm * Wm, quads = plane / 4;   // (host: Wm % 4 == 0, so a quad lies in one row)
+    uint8_t* fn = err + 2 * (int64_t)blockIdx.y * plane;
+    uint8_t* fp = fn + plane;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
+        const int r = (int)(4 * q / Wm), c = (int)(4 * q - (int64_t)r * Wm);
+        uint8_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        if (r < d.H) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (c + u < d.W) {
+                    const int64_t i = (int64_t)r * d.W + c + u;
+                    const bool p = d.mask[i] != 0, g = d.gt[i] != 0, v = d.valid[i] != 0;
+                    a[u] = (g && !p && v) ? 1 : 0;
+                    b[u] = (!g && p && v) ? 1 : 0;
+                }
+            }
+        }
+        *reinterpret_cast<uchar4*>(fn + 4 * q) = make_uchar4(a[0], a[1], a[2], a[3]);
+        *reinterpret_cast<uchar4*>(fp + 4 * q) = make_uchar4(b[0], b[1], b[2], b[3]);
+    }
+}
+
+// keys (float bits of max(dist * keep)) << 32 | (0xFFFFFFFF - first raster index): vpu_masked_argmax's packing
+__global__ __launch_bounds__(256) void click_argmax_kernel(const vpu_eval_obj* __restrict__ objs, const float* __restrict__ dist,
+                                                           int Hm, int Wm) {
+    const int b = blockIdx.y >> 1, e = blockIdx.y & 1;
+    const vpu_eval_obj& d = objs[b];
+    const float* dd = dist + (int64_t)blockIdx.y * Hm * Wm;
+    const int HW = d.H * d.W;
+    unsigned long long best = 0ull;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+        const int r = i / d.W, c = i - r * d.W;
+        const float v = d.keep[i] ? dd[(int64_t)r * Wm + c] : 0.0f;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (0xFFFFFFFFu - (unsigned)i);
+        best = key > best ? key : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(best, o, 64);
+        best = t > best ? t : best;
+    }
+    __shared__ unsigned long long red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) best = red[k] > best ? red[k] : best;
+        atomicMax(reinterpret_cast<unsigned long long*>(d.out) + e, best);
+    }
+}
+
+}  // namespace
+
+extern "C" int vpu_roi_resize_batched(const vpu_eval_obj* objs, int32_t n, float* out, int32_t S_h, int32_t S_w, int32_t flip,
+                                      int32_t channels, void* stream) {
+    vpu_clear_stale_error();
+    if (!objs || !out || n < 1 || n > 65535 || S_h < 1 || S_w < 4 || S_w % 4 || (channels != 3 && channels != 4)) {
+        vpu_set_error("roi_resize_batched: sizes (1 <= n <= 65535, S_w a multiple of 4, 3 or 4 channels)");
+        return VPU_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(out) % 16) { vpu_set_error("roi_resize_batched: out not 16-byte aligned"); return VPU_ERR_ALIGN; }
+    const int nb = vpu_grid_for((long long)channels * S_h * (S_w / 4), 256, 256);
+    roi_resize_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, n, out, S_h, S_w, flip, channels);
+    return vpu_check_launch("vpu_roi_resize_batched");
+}
+
+extern "C" int vpu_roi_paste_batched(const vpu_eval_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w,
+                                     float pred_thr, float box_thr, int32_t max_hw, void* stream) {
+    vpu_clear_stale_error();
+    if (!objs || !probs || n < 1 || n > 65535 || S_h < 1 || S_w < 1 || max_hw < 1) {
+        vpu_set_error("roi_paste_batched: sizes (1 <= n <= 65535)");
+        return VPU_ERR_ARG;
+    }
+    paste_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    const int nb = vpu_grid_for(((long long)max_hw + 3) / 4, 256, 128);
+    roi_paste_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, probs, S_h, S_w, pred_thr, box_thr);
+    return vpu_check_launch("vpu_roi_paste_batched");
+}
+
+extern "C" int vpu_click_keys_batched(const vpu_eval_obj* objs, int32_t n, uint8_t* err, int32_t* scratch, float* dist,
+                                      int32_t Hm, int32_t Wm, int32_t max_hw, void* stream) {
+    vpu_clear_stale_error();
+    if (!objs || !err || !scratch || !dist || n < 1 || n > 32767 || Hm < 1 || Wm < 4 || Wm % 4 || max_hw < 1) {
+        vpu_set_error("click_keys_batched: sizes (1 <= n <= 32767, Wm a multiple of 4)");
+        return VPU_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(err) % 4) { vpu_set_error("click_keys_batched: err not 4-byte aligned"); return VPU_ERR_ALIGN; }
+    const int nb = vpu_grid_for((long long)Hm * Wm / 4, 256, 128);
+    click_err_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, err, Hm, Wm);
+    int rc = vpu_check_launch("vpu_click_keys_batched (error masks)");
+    if (rc) return rc;
+    rc = vpu_edt(err, scratch, dist, 2 * n, Hm, Wm, 1, stream);
+    if (rc) return rc;
+    vpu_clear_stale_error();
+    const int na = vpu_grid_for(max_hw, 2048, 128);
+    click_argmax_kernel<<<dim3((unsigned)na, (unsigned)(2 * n)), 256, 0, ST>>>(objs, dist, Hm, Wm);
+    return vpu_check_launch("vpu_click_keys_batched (arg-max)");
+}

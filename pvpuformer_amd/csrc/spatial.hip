@@ -3,6 +3,7 @@
 // DMA gates, conv_seg, final align_corners=True upsample.  All HBM-bound: vector accesses, fp32 math.
 #include <stdlib.h>
 #include "vpu_common.h"
+#include "interp_ac.h"
 #include "../../include/vpu_hip.h"
 
 #define DISPATCH_T(dtype, ...)                                   \
@@ -1436,27 +1437,15 @@ __global__ __launch_bounds__(256) void head_grad_fused_kernel(const bf16_t* __re
 }
 
 // ------------------------------------------------------------------------------ align_corners=True upsample (planes)
-__device__ __forceinline__ void src_index_ac(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
-    const float s = scale * (float)dst;
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-}
+// (src_index_ac, ac_scale, ac_sample: interp_ac.h, shared with the batched NoBRS kernels of evalbatch.hip)
 __global__ __launch_bounds__(256) void upsample_ac_fwd_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                               int64_t planes, int h, int w, int H, int W) {
-    const float sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+    const float sh = ac_scale(h, H), sw = ac_scale(w, W);
     const int64_t total = planes * H * W;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int X = (int)(i % W), Y = (int)((i / W) % H);
         const int64_t pl = i / ((int64_t)W * H);
-        int y0, y1, x0, x1; float ly, lx;
-        src_index_ac(Y, sh, h, y0, y1, ly);
-        src_index_ac(X, sw, w, x0, x1, lx);
-        const float* p = in + pl * h * w;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        out[i] = hy * (hx * p[y0 * w + x0] + lx * p[y0 * w + x1]) + ly * (hx * p[y1 * w + x0] + lx * p[y1 * w + x1]);
+        out[i] = ac_sample(in + pl * h * w, w, h, w, sh, sw, Y, X);
     }
 }
 __global__ __launch_bounds__(256) void upsample_ac_bwd_kernel(const float* __restrict__ dout, float* __restrict__ din,

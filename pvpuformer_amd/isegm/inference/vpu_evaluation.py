@@ -5,12 +5,13 @@ last probability map).  Per click: the Clicker puts the next oracle click at the
 region, the predictor runs the network on (image, previous prediction, clicks [+ box prompt]) through its transform
 pipeline, the IoU at ``pred_thr`` is recorded, and the loop stops once ``max_iou_thr`` is reached after ``min_clicks``.
 As shipped the reference always evaluates with click prompts (``as_prompt_type = 0``, vpu_evaluation.py:51)."""
+import os
 import time
 
 import numpy as np
 import torch
 
-from . import utils
+from . import batched, utils
 from .clicker import Clicker
 
 
@@ -57,13 +58,40 @@ def _evaluate_sample(image, gt_mask, predictor, max_iou_thr, pred_thr, min_click
     return (clicker.clicks_list if clicker is not None else []), np.array(ious, dtype=np.float32), probs
 
 
-def evaluate_dataset(dataset, predictor, **kwargs):
+def evaluate_dataset(dataset, predictor, batch_objects=None, **kwargs):
     """``dataset``: anything with ``len()`` and ``get_sample(i)`` returning an object with ``image``, ``objects_ids``
-    and ``gt_mask(object_id)`` (the contract of the reference's isegm.data datasets)."""
+    and ``gt_mask(object_id)`` (the contract of the reference's isegm.data datasets).
+
+    ``batch_objects`` (not in the reference; default: environment ``VPU_EVAL_BATCH``, else 1): K > 1 evaluates up to K
+    objects at once, in lock-step through one batched forward per click (``batched.BatchedEvaluator``), and returns the
+    same per-object IoU series in the same order.  That path applies only to a ``BasePredictor`` whose transforms are
+    [ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip], without ``callback`` and with
+    ``as_prompt_type == 0``; in every other case the objects are silently evaluated one at a time, as with K = 1."""
+    if batch_objects is None:
+        batch_objects = int(os.environ.get("VPU_EVAL_BATCH", "1") or 1)
+    if batch_objects > 1 and kwargs.get("max_clicks", 20) >= 1 and \
+            batched.batchable(predictor, kwargs.get("callback"), kwargs.get("as_prompt_type", 0)):
+        return _evaluate_dataset_batched(dataset, predictor, batch_objects, **kwargs)
     started = time.time()
     series = []
     for index in range(len(dataset)):
         sample = dataset.get_sample(index)
         series += [evaluate_sample(sample.image, sample.gt_mask(oid), predictor, sample_id=index, **kwargs)[1]
                    for oid in sample.objects_ids]
+    return series, time.time() - started
+
+
+def dataset_objects(dataset):
+    """(image, ground truth) of every object, in dataset order, then ``objects_ids`` order."""
+    for index in range(len(dataset)):
+        sample = dataset.get_sample(index)
+        for oid in sample.objects_ids:
+            yield sample.image, sample.gt_mask(oid)
+
+
+def _evaluate_dataset_batched(dataset, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20,
+                              callback=None, as_prompt_type=0):
+    started = time.time()
+    runner = batched.BatchedEvaluator(predictor, batch_objects, max_iou_thr, pred_thr, min_clicks, max_clicks)
+    series = [ious for _, ious in runner.run(dataset_objects(dataset))]
     return series, time.time() - started

@@ -436,6 +436,24 @@ def masked_argmax(dist, keep_u8):
     return out
 
 
+def roi_resize_batched(objs, n, out, S_h, S_w, flip, channels):
+    """Network input of n objects (objs: device array of vpu_eval_obj) -> out fp32 [2n or n, channels, S_h, S_w]."""
+    _lib.call("vpu_roi_resize_batched", ptr(objs), n, ptr(out), S_h, S_w, int(flip), channels, _stream())
+
+
+def roi_paste_batched(objs, n, probs, S_h, S_w, pred_thr, box_thr, max_hw):
+    """probs fp32 [*, S_h, S_w] pasted into the objects' canvases, with mask, IoU counts and box (vpu_roi_paste_batched)."""
+    _lib.call("vpu_roi_paste_batched", ptr(objs), n, ptr(probs), S_h, S_w, float(pred_thr), float(box_thr), max_hw, _stream())
+
+
+def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
+    """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
+    err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)
+    scratch = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.int32)
+    dist = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.float32)
+    _lib.call("vpu_click_keys_batched", ptr(objs), n, ptr(err), ptr(scratch), ptr(dist), Hm, Wm, max_hw, _stream())
+
+
 def disk_maps(points, boxes, out, B, n, H, W, radius):
     _lib.call("vpu_disk_maps", ptr(points), ptr(boxes), ptr(out), B, n, H, W, float(radius), _stream())
 

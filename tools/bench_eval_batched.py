@@ -1,0 +1,98 @@
+#!/usr/bin/env python
+"""Throughput of the NoBRS evaluation with K objects per forward (evaluate_dataset(batch_objects=K)): ViT-B/448 bf16,
+flip TTA, ZoomIn to 448 x 448 from the first click, a 20-click budget that no object stops early (max_iou_thr=2), over a
+synthetic set of objects on images of mixed sizes (448 x 448, 480 x 640, 375 x 500).  Prints one JSON line: object-clicks
+per second for each K, and the share of the time spent in the model forward (a second, synchronised pass).
+usage: python tools/bench_eval_batched.py [objects] [K ...]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from pvpuformer_amd.isegm.inference.predictors import get_predictor            # noqa: E402
+from pvpuformer_amd.isegm.inference.vpu_evaluation import evaluate_dataset      # noqa: E402
+from pvpuformer_amd.isegm.model.is_vpu_model import VitMultiGaussianVector_ed_Model   # noqa: E402
+from pvpuformer_amd.synth import synth_batch, vitb_model_kwargs                # noqa: E402
+
+SIZES = [(448, 448), (480, 640), (375, 500)]
+
+
+class Sample:
+    def __init__(self, image, masks):
+        self.image, self._masks, self.objects_ids = image, masks, list(range(len(masks)))
+
+    def gt_mask(self, oid):
+        return self._masks[oid]
+
+
+class Dataset:
+    def __init__(self, n_objects, per_image=2):
+        self.samples = []
+        for i in range((n_objects + per_image - 1) // per_image):
+            H, W = SIZES[i % len(SIZES)]
+            b = synth_batch(per_image, max(H, W), seed=100 + i)
+            image = (b["images"][0, :, :H, :W].permute(1, 2, 0).numpy() * 255).astype(np.uint8)
+            k = min(per_image, n_objects - i * per_image)
+            self.samples.append(Sample(image, [b["instances"][j, 0, :H, :W].numpy().astype(np.int32) for j in range(k)]))
+
+    def __len__(self):
+        return len(self.samples)
+
+    def get_sample(self, i):
+        return self.samples[i]
+
+
+def main():
+    n_obj = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    ks = [int(k) for k in sys.argv[2:]] or [1, 4, 8, 16]
+    torch.manual_seed(0)
+    model = VitMultiGaussianVector_ed_Model(**vitb_model_kwargs()).cuda()
+    model.set_compute_dtype("bf16")
+    model.eval()
+    model.weights_frozen = True
+    ds, warm = Dataset(n_obj), Dataset(max(ks) + 2)
+    kw = dict(max_iou_thr=2.0, pred_thr=0.49, max_clicks=20)
+    mk = lambda: get_predictor(model, "NoBRS", "cuda", with_flip=True,
+                               zoom_in_params=dict(skip_clicks=-1, target_size=(448, 448)))
+    res = {}
+    for K in ks:
+        evaluate_dataset(warm, mk(), batch_objects=K, max_iou_thr=2.0, max_clicks=3)     # warm-up (kernels, shapes)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        series, _ = evaluate_dataset(ds, mk(), batch_objects=K, **kw)
+        torch.cuda.synchronize()
+        secs = time.perf_counter() - t0
+        clicks = sum(len(s) for s in series)
+        # forward share: the same run with the forward synchronised on both sides
+        fwd = []
+        orig = model.forward
+
+        def timed(*a, **k):
+            torch.cuda.synchronize(); t = time.perf_counter()
+            out = orig(*a, **k)
+            torch.cuda.synchronize(); fwd.append(time.perf_counter() - t)
+            return out
+        model.forward = timed
+        try:
+            t1 = time.perf_counter()
+            evaluate_dataset(ds, mk(), batch_objects=K, **kw)
+            secs_sync = time.perf_counter() - t1
+        finally:
+            model.forward = orig
+        res[K] = dict(object_clicks_per_s=round(clicks / secs, 1), ms_per_step=round(secs / len(fwd) * 1e3, 2),
+                      forwards=len(fwd), forward_share=round(sum(fwd) / secs_sync, 3), object_clicks=clicks)
+    k1 = res.get(1, {}).get("object_clicks_per_s")
+    line = {"bench": "eval_batched", "model": "vitb448", "dtype": "bf16", "objects": n_obj, "max_clicks": 20,
+            "results": {str(k): v for k, v in res.items()}}
+    if k1:
+        line["speedup_vs_k1"] = {str(k): round(v["object_clicks_per_s"] / k1, 2) for k, v in res.items()}
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
