@@ -348,6 +348,30 @@ int vpu_roi_paste_batched(const vpu_eval_obj* objs, int32_t n, const float* prob
  * uint8, scratch int32 and dist fp32, each [2n][Hm][Wm], Hm >= every H, Wm >= every W, Wm % 4 == 0; max_hw >= every H * W. */
 int vpu_click_keys_batched(const vpu_eval_obj* objs, int32_t n, uint8_t* err, int32_t* scratch, float* dist, int32_t Hm,
                            int32_t Wm, int32_t max_hw, void* stream);
+/* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
+ * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
+ *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the
+ *   float ground truth 1 / 0 / -1), the inclusive roi (whole image when the object has none), mirror != 0: the flip copy,
+ *   which reads source column W - 1 - c inside the UN-mirrored roi (the reference flips first and crops with the same roi),
+ *   n_obj = rows per polarity of the object's own click layout, max(#positive, #negative, 1). */
+typedef struct vpu_box_row {
+    const float* prev;
+    const uint8_t* gt;
+    const uint8_t* valid;
+    int32_t H, W, r0, r1, c0, c1, mirror, n_obj;
+} vpu_box_row;
+/* boxes int32 [n_rows][5] = (x_center, y_center, width, height, slot) of every row, all zero unless all four are >= 1:
+ * gt and prev sampled over the roi to (S_h, S_w) (vpu_upsample_ac_fwd's formula; a crop of that size is copied), fn = gt > 0.5
+ * & prev < pred_thresh, fp = !(gt > 0.5) & prev > pred_thresh, the larger of the two (fn only when strictly larger), its
+ * 8-connected components (vpu_cc_roots / vpu_cc_table over all rows), the region max_connected_regions keeps, its bounding
+ * box.  slot: computed in the object's own click layout and moved into the padded one of points fp32 [n_rows][2 * n_batch][3]:
+ * fn -> n_obj - 1; fp -> n_batch + j, j the first negative row of the object with order < 0, else n_obj - 1.
+ * flag[0] = 1 when the rows together have more than kmax components (then boxes is not valid), else 0.
+ * Scratch: masks uint8 [n_rows][S_h][S_w], counts int32 [n_rows][2], roots and slots int32 [n_rows][S_h][S_w], table int32
+ * [6 * kmax + 1].  n_rows * S_h * S_w < 2^31.  Neither allocates nor synchronises. */
+int vpu_box_prompts_batched(const vpu_box_row* rows, int32_t n_rows, const float* points, int32_t n_batch, int32_t S_h,
+                            int32_t S_w, float pred_thresh, uint8_t* masks, int32_t* counts, int32_t* roots, int32_t* slots,
+                            int32_t* table, int32_t kmax, int32_t* boxes, int32_t* flag, void* stream);
 /* 8-connected components of B masks [B][H][W]: roots[i] = smallest linear index (within the whole [B][H][W] array) of the
  * component of non-zero pixel i, -1 on zero pixels.  Sorted by root, the components are in the raster order of their first
  * pixel -- the label order of the reference's skimage.measure.label(connectivity=2) in max_connected_regions

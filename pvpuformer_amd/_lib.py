@@ -59,6 +59,13 @@ class EvalObj(C.Structure):
                 ("c1", C.c_int32), ("src", C.c_int32), ("clear_at", C.c_int32)]
 
 
+class BoxRow(C.Structure):
+    """vpu_box_row (include/vpu_hip.h): one row (an object or its flip copy) of vpu_box_prompts_batched."""
+    _fields_ = [("prev", C.c_void_p), ("gt", C.c_void_p), ("valid", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("r0", C.c_int32), ("r1", C.c_int32), ("c0", C.c_int32),
+                ("c1", C.c_int32), ("mirror", C.c_int32), ("n_obj", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -106,6 +113,7 @@ SIGNATURES = {
     "vpu_roi_resize_batched": [_P, _I, _P, _I, _I, _I, _I, _P],
     "vpu_roi_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
+    "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_disk_maps": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vpu_patch_im2col": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_patch_im2col_prenorm": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

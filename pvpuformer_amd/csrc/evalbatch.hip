@@ -203,7 +203,181 @@ __global__ __launch_bounds__(256) void click_argmax_kernel(const vpu_eval_obj* _
     }
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (4) box prompts of a size group (BasePredictor.get_vqu_prediction, base.py:114-121, then cal_box(as_allmask=False,
+//     jitter_box=False)): one row per object and, with flip, one more per object's flip copy.
+//     box_masks_kernel: ground truth (1 / 0 / -1 where ignored, the float values the sequential path resizes) and previous
+//       prediction sampled over the row's roi to (S_h, S_w) with ac_sample's formula, thresholded to the false-negative
+//       (bit 0) and false-positive (bit 1) masks, and their pixel counts.  A flip row reads source column W - 1 - c
+//       INSIDE THE UN-MIRRORED roi: the sequential code flips the full planes first and crops them with the same roi.
+//     box_choose_kernel: the larger of the two masks (fn when count(fn) > count(fp)), selected on the device.
+//     vpu_cc_roots / vpu_cc_table over the R chosen planes, then box_finish_kernel, one block per row.
+__device__ __forceinline__ float box_gt_at(const vpu_box_row& d, int r, int c) {
+    const int64_t i = (int64_t)r * d.W + (d.mirror ? d.W - 1 - c : c);
+    return d.gt[i] ? 1.f : (d.valid[i] ? 0.f : -1.f);
+}
+__device__ __forceinline__ float box_prev_at(const vpu_box_row& d, int r, int c) {
+    return d.prev[(int64_t)r * d.W + (d.mirror ? d.W - 1 - c : c)];
+}
+
+__global__ __launch_bounds__(256) void box_masks_kernel(const vpu_box_row* __restrict__ rows, uint8_t* __restrict__ masks,
+                                                        int* __restrict__ counts, int S_h, int S_w, float pred_thresh) {
+    const vpu_box_row& d = rows[blockIdx.y];
+    const int h = d.r1 - d.r0 + 1, w = d.c1 - d.c0 + 1;
+    const bool copy = h == S_h && w == S_w;
+    const float sh = ac_scale(h, S_h), sw = ac_scale(w, S_w);
+    const int total = S_h * S_w;
+    uint8_t* out = masks + (int64_t)blockIdx.y * total;
+    int nfn = 0, nfp = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int Y = i / S_w, X = i - Y * S_w;
+        float g, p;
+        if (copy) {
+            g = box_gt_at(d, d.r0 + Y, d.c0 + X);
+            p = box_prev_at(d, d.r0 + Y, d.c0 + X);
+        } else {        // ac_sample (interp_ac.h), the same expression in the same order, on the crop's pixels
+            int y0, y1, x0, x1; float ly, lx;
+            src_index_ac(Y, sh, h, y0, y1, ly);
+            src_index_ac(X, sw, w, x0, x1, lx);
+            const float hy = 1.f - ly, hx = 1.f - lx;
+            y0 += d.r0; y1 += d.r0; x0 += d.c0; x1 += d.c0;
+            g = hy * (hx * box_gt_at(d, y0, x0) + lx * box_gt_at(d, y0, x1)) +
+                ly * (hx * box_gt_at(d, y1, x0) + lx * box_gt_at(d, y1, x1));
+            p = hy * (hx * box_prev_at(d, y0, x0) + lx * box_prev_at(d, y0, x1)) +
+                ly * (hx * box_prev_at(d, y1, x0) + lx * box_prev_at(d, y1, x1));
+        }
+        const bool gt = g > 0.5f;
+        const bool fn = gt && p < pred_thresh, fp = !gt && p > pred_thresh;
+        out[i] = (uint8_t)((fn ? 1 : 0) | (fp ? 2 : 0));
+        nfn += fn ? 1 : 0;
+        nfp += fp ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { nfn += __shfl_xor(nfn, o, 64); nfp += __shfl_xor(nfp, o, 64); }
+    __shared__ int red[4][2];
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = nfn; red[threadIdx.x >> 6][1] = nfp; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (v) atomicAdd(counts + 2 * blockIdx.y + threadIdx.x, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void box_choose_kernel(uint8_t* __restrict__ masks, const int* __restrict__ counts, int total) {
+    const int shift = counts[2 * blockIdx.y] > counts[2 * blockIdx.y + 1] ? 0 : 1;      // cal_box: fn only when strictly larger
+    uint8_t* m = masks + (int64_t)blockIdx.y * total;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) m[i] = (m[i] >> shift) & 1;
+}
+
+// max_connected_regions (trainer.py:1175-1190; prompt_sim._kept_region_boxes) scans a row's components in ascending root
+// (= label) order, tracks the largest so far (first one on ties), re-targets every component with cnt > 0.1 * total onto
+// the largest so far and keeps the components whose target is the final largest M.  In closed form, with M the
+// component of maximal count and, among those, the smallest root: the largest-so-far at component j is M exactly when
+// root_j >= root_M (M is the FIRST to reach the maximum, and nothing after it exceeds it), and a component that is not
+// re-targeted keeps its own label, which is M only for M itself.  So kept = {M} + {j : root_j > root_M and
+// cnt_j > 0.1 * total}, which needs no sorted table: two order-free block reductions over the rows of vpu_cc_table.
+// The comparison is the reference's, in double.
+__global__ __launch_bounds__(256) void box_finish_kernel(const vpu_box_row* __restrict__ rows, const float* __restrict__ points,
+                                                         const int* __restrict__ counts, const int* __restrict__ table, int kmax,
+                                                         int n_batch, int plane, int* __restrict__ boxes, int* __restrict__ flag) {
+    const int row = blockIdx.x, wave = threadIdx.x >> 6;
+    const int found = table[6 * (int64_t)kmax];
+    const int K = found < kmax ? found : kmax;
+    if (row == 0 && threadIdx.x == 0) *flag = found > kmax ? 1 : 0;      // table truncated: the host derives this step's boxes
+    const int lo = row * plane, hi = lo + plane;           // (host: rows * plane < 2^31)
+    __shared__ unsigned long long red_key[4];
+    __shared__ long long red_sum[4];
+    __shared__ int red_box[4][4];
+    unsigned long long best = 0ull;
+    long long total = 0;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int root = table[6 * k], cnt = table[6 * k + 1];
+        if (root >= lo && root < hi) {
+            total += cnt;
+            const unsigned long long key = ((unsigned long long)(unsigned)cnt << 32) | (0xFFFFFFFFu - (unsigned)root);
+            best = key > best ? key : best;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(best, o, 64);
+        best = t > best ? t : best;
+        total += __shfl_xor(total, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { red_key[wave] = best; red_sum[wave] = total; }
+    __syncthreads();
+    best = red_key[0]; total = red_sum[0];
+    for (int k = 1; k < 4; ++k) { best = red_key[k] > best ? red_key[k] : best; total += red_sum[k]; }
+    const int m_root = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+    const double tenth = 0.1 * (double)total;
+    int y0 = 0x7fffffff, y1 = -1, x0 = 0x7fffffff, x1 = -1;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        const int* t = table + 6 * k;
+        const int root = t[0];
+        if (root >= lo && root < hi && (root == m_root || (root > m_root && (double)t[1] > tenth))) {
+            y0 = min(y0, t[2]); y1 = max(y1, t[3]); x0 = min(x0, t[4]); x1 = max(x1, t[5]);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        y0 = min(y0, __shfl_xor(y0, o, 64)); y1 = max(y1, __shfl_xor(y1, o, 64));
+        x0 = min(x0, __shfl_xor(x0, o, 64)); x1 = max(x1, __shfl_xor(x1, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { red_box[wave][0] = y0; red_box[wave][1] = y1; red_box[wave][2] = x0; red_box[wave][3] = x1; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 1; k < 4; ++k) {
+        y0 = min(y0, red_box[k][0]); y1 = max(y1, red_box[k][1]); x0 = min(x0, red_box[k][2]); x1 = max(x1, red_box[k][3]);
+    }
+    int out[5] = {0, 0, 0, 0, 0};
+    if (best != 0ull) {
+        // the slot in the object's own click layout (n_obj rows per polarity) moved into the padded one (n_batch rows):
+        // fn: the last positive row n_obj - 1 of both; fp: the first free negative row n_obj + j (default j = n_obj - 1)
+        // is row n_batch + j of the padded layout
+        const int n_obj = rows[row].n_obj;
+        int slot = n_obj - 1;
+        if (!(counts[2 * row] > counts[2 * row + 1])) {
+            int j = n_obj - 1;
+            const float* neg = points + ((int64_t)row * 2 * n_batch + n_batch) * 3;
+            for (int q = 0; q < n_obj; ++q)
+                if (neg[3 * q + 2] < 0.f) { j = q; break; }
+            slot = n_batch + j;
+        }
+        const int xc = (x0 + x1) >> 1, yc = (y0 + y1) >> 1, bw = x1 - x0, bh = y1 - y0;
+        if (xc >= 1 && yc >= 1 && bw >= 1 && bh >= 1) { out[0] = xc; out[1] = yc; out[2] = bw; out[3] = bh; out[4] = slot; }
+    }
+    for (int k = 0; k < 5; ++k) boxes[5 * row + k] = out[k];
+}
+
 }  // namespace
+
+extern "C" int vpu_box_prompts_batched(const vpu_box_row* rows, int32_t n_rows, const float* points, int32_t n_batch, int32_t S_h,
+                                       int32_t S_w, float pred_thresh, uint8_t* masks, int32_t* counts, int32_t* roots,
+                                       int32_t* slots, int32_t* table, int32_t kmax, int32_t* boxes, int32_t* flag, void* stream) {
+    vpu_clear_stale_error();
+    const int64_t total = (int64_t)n_rows * S_h * S_w;
+    if (!rows || !points || !masks || !counts || !roots || !slots || !table || !boxes || !flag || n_rows < 1 || n_rows > 65535 ||
+        n_batch < 1 || S_h < 1 || S_w < 1 || kmax < 1 || total >= 0x7FFFFFFFLL) {
+        vpu_set_error("box_prompts_batched: null pointer or sizes (1 <= n_rows <= 65535, n_rows * S_h * S_w < 2^31)");
+        return VPU_ERR_ARG;
+    }
+    if (hipMemsetAsync(counts, 0, 2 * sizeof(int32_t) * n_rows, ST) != hipSuccess) {
+        vpu_set_error("box_prompts_batched: memset");
+        return VPU_ERR_LAUNCH;
+    }
+    const int nb = vpu_grid_for((long long)S_h * S_w, 256, 128);
+    box_masks_kernel<<<dim3((unsigned)nb, (unsigned)n_rows), 256, 0, ST>>>(rows, masks, counts, S_h, S_w, pred_thresh);
+    box_choose_kernel<<<dim3((unsigned)nb, (unsigned)n_rows), 256, 0, ST>>>(masks, counts, S_h * S_w);
+    int rc = vpu_check_launch("vpu_box_prompts_batched (masks)");
+    if (rc) return rc;
+    rc = vpu_cc_roots(masks, roots, n_rows, S_h, S_w, stream);
+    if (rc) return rc;
+    rc = vpu_cc_table(roots, slots, table, kmax, n_rows, S_h, S_w, stream);
+    if (rc) return rc;
+    vpu_clear_stale_error();
+    box_finish_kernel<<<(unsigned)n_rows, 256, 0, ST>>>(rows, points, counts, table, kmax, n_batch, S_h * S_w, boxes, flag);
+    return vpu_check_launch("vpu_box_prompts_batched (boxes)");
+}
 
 extern "C" int vpu_roi_resize_batched(const vpu_eval_obj* objs, int32_t n, float* out, int32_t S_h, int32_t S_w, int32_t flip,
                                       int32_t channels, void* stream) {

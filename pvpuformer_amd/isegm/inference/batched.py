@@ -15,7 +15,30 @@ The results equal the sequential loop's object by object: every per-object opera
 interpolation formula, same counts, same keys); what the batch shares is only the network, whose click tokens are padded
 to a common count with not-a-point rows that the network ignores.  ``evaluate_dataset`` dispatches here; see
 ``batchable`` for when it may.  The same scheduler runs on the host with torch / scipy stand-ins of the three kernels
-(``_HostOps``), which is what the CPU tests check it with."""
+(``_HostOps``), which is what the CPU tests check it with.
+
+Box prompts (``as_prompt_type=1``).  ``BasePredictor.get_vqu_prediction`` derives the box of every click from the previous
+prediction and the ground truth (``prompt_sim.get_next_promts``: several read-backs, a host scan over the connected
+components, and a simulated next click that is thrown away).  Here ``vpu_box_prompts_batched`` derives the boxes of all
+rows of a size group on the device, between the resize and the forward, and hands the ``int32 [rows, 5]`` tensor to the
+network: the step keeps its one read-back.  Reproduced as the sequential path has them:
+
+* the flip copy's box is NOT the mirror image of the straight one: the sequential code flips ground truth and previous
+  prediction first and crops both with the same, un-mirrored ZoomIn roi, so that row reads source column ``W - 1 - c``
+  inside the un-mirrored roi;
+* ``max_connected_regions``' merge rule (every component above 10 % of the foreground joins the largest so far);
+* the slot: computed in the object's own click layout (``n_obj = max(#positive, #negative, 1)`` rows per polarity) and
+  moved into the batch's padded layout (``_padded_slot``); in the false-negative case it is the object's last positive
+  row, which may hold a real click that the box then replaces, as in the reference;
+* the ground truth is resized as the float values 1 / 0 / -1 (ignore), which is what the sequential path uploads;
+* a click whose ZoomIn recalculation fires is re-run by ``get_prediction``, which is click-only: an object with ``recalc``
+  set re-runs as prompt type 0, so the groups of a step are keyed by (size, prompt type).
+
+More components in a group than the kernel's table holds (salt-and-pepper masks; 1024 per row) raise a flag that comes
+back with the read-back; the forward of that group is discarded and its objects repeat the click with boxes from the host
+code (``_host_boxes``: ``crop_resize`` + ``prompt_sim.cal_box``, also ``_HostOps``' stand-in).  The sequential path also
+runs ``prompt_sim.next_click`` on every box-prompt click and so advances the global numpy generator for a click it
+discards; the batched path does not.  No result depends on it (the evaluation clicks come from the Clicker)."""
 import ctypes as C
 import struct
 
@@ -23,18 +46,21 @@ import numpy as np
 import torch
 
 from .clicker import Click
-from .transforms import AddHorizontalFlip, Roi, SigmoidForPred, ZoomIn
+from .transforms import AddHorizontalFlip, Roi, SigmoidForPred, ZoomIn, crop_resize
 
 _STATS = 2           # int64 offset of the int32 statistics in an object's 6-int64 output slot
 _MASK64 = 0xFFFFFFFFFFFFFFFF
+_BOX_PRED_THRESH = 0.49    # get_next_promts' default pred_thresh (get_vqu_prediction does not pass one)
+_FLAGS_PER_ROW = 12        # int32 flags in one 48-byte row appended to the read-back
 
 
 def batchable(predictor, callback=None, as_prompt_type=0):
     """True when ``evaluate_dataset`` may run ``predictor`` batched: a ``BasePredictor`` whose transforms are only
     [ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip] (in that order, each optional), no
-    callback and click prompts (``as_prompt_type == 0``)."""
+    callback and click or box prompts (``as_prompt_type`` 0 or 1; ``get_vqu_prediction`` passes no scribbles, so type 2
+    stays sequential)."""
     from .predictors.base import BasePredictor
-    if not isinstance(predictor, BasePredictor) or callback is not None or as_prompt_type != 0:
+    if not isinstance(predictor, BasePredictor) or callback is not None or as_prompt_type not in (0, 1):
         return False
     ts, i = list(predictor.transforms), 0
     if i < len(ts) and type(ts[i]) is ZoomIn:
@@ -67,6 +93,37 @@ def _load_image(image, device):
     return image.float().contiguous()
 
 
+def _padded_slot(loc, n_obj, n_batch):
+    """Slot ``loc`` of an object's own click layout (``n_obj`` rows per polarity) in the layout padded to ``n_batch`` rows."""
+    return loc if loc < n_obj else n_batch + (loc - n_obj)
+
+
+def _host_boxes(rows, points_nd, n_batch, size, target_size, pred_thresh=_BOX_PRED_THRESH):
+    """Box prompts int32 [len(rows), 5] by the sequential recipe (base.py:114-121 + cal_box) for ``rows`` = (object, roi or
+    None, mirror, n_obj), one per row of ``points_nd`` [rows, 2 * n_batch, 3].  Each row is computed alone, as the
+    sequential call does its two."""
+    from ..engine.prompt_sim import cal_box
+    out = np.zeros((len(rows), 5), np.int32)
+    pts = points_nd.detach().float().cpu().numpy()
+    for i, (o, roi, mirror, n_obj) in enumerate(rows):
+        gt = torch.where(o.gt != 0, 1.0, torch.where(o.valid != 0, 0.0, -1.0)).float()[None, None]
+        prev = o.canvas[o.prev][None, None]
+        if mirror:
+            gt, prev = torch.flip(gt, dims=[3]), torch.flip(prev, dims=[3])
+        if roi is not None:
+            gt, prev = crop_resize(gt, roi, target_size), crop_resize(prev, roi, target_size)
+        assert tuple(gt.shape[2:]) == tuple(size)
+        g = gt.cpu().numpy()[:, 0] > 0.5
+        p = prev.float().cpu().numpy()[:, 0]
+        fn, fp = np.logical_and(g, p < pred_thresh), np.logical_and(np.logical_not(g), p > pred_thresh)
+        own = np.concatenate([pts[i, :n_obj], pts[i, n_batch:n_batch + n_obj]], 0)[None]
+        box = cal_box(g, fn, fp, own, as_allmask=False, jitter_box=False)[0]
+        if box.any():
+            box[4] = _padded_slot(int(box[4]), n_obj, n_batch)
+        out[i] = box
+    return out
+
+
 class _Object:
     """One object's evaluation state (a slot of the batch)."""
 
@@ -87,6 +144,7 @@ class _Object:
         self.keys = None               # click keys of the current mask
         self.clear_at = -1             # pixel of the click made this step (cleared in the not-clicked map)
         self.recalc = False            # re-run the current click (ZoomIn.check_possible_recalculation fired)
+        self.host_box = False          # re-run the current click with boxes from the host (component table overflow)
         self.done = False
         self.plan = None
 
@@ -99,9 +157,10 @@ class _DeviceOps:
         self._lib, self.ops, self.device = _lib, ops, torch.device(device)
         self._desc = []
 
-    def begin(self, n_out):
-        self._desc = []
-        self.out = torch.empty(max(n_out, 1), 6, device=self.device, dtype=torch.int64)
+    def begin(self, n_out, n_flags=0):
+        self._desc, self._box, self.n_out = [], [], max(n_out, 1)
+        self.out = torch.empty(self.n_out + (n_flags + _FLAGS_PER_ROW - 1) // _FLAGS_PER_ROW, 6, device=self.device,
+                               dtype=torch.int64)
 
     def add(self, o, roi, src, out_row, prev=True):
         """Appends one descriptor; returns its index."""
@@ -120,10 +179,24 @@ class _DeviceOps:
         self._desc.append(d)
         return len(self._desc) - 1
 
+    def add_box(self, o, roi, mirror, n_obj):
+        """Appends one row of the box-prompt kernel (``roi`` None: the whole image); returns its index."""
+        r0, r1, c0, c1 = roi if roi is not None else Roi.whole(o.H, o.W)
+        assert 0 <= r0 <= r1 < o.H and 0 <= c0 <= c1 < o.W and n_obj >= 1, (roi, o.H, o.W, n_obj)
+        d = self._lib.BoxRow()
+        d.prev, d.gt, d.valid = o.canvas[o.prev].data_ptr(), o.gt.data_ptr(), o.valid.data_ptr()
+        d.H, d.W = o.H, o.W
+        d.r0, d.r1, d.c0, d.c1 = r0, r1, c0, c1
+        d.mirror, d.n_obj = int(mirror), int(n_obj)
+        self._box.append(d)
+        return len(self._box) - 1
+
     def upload(self):
         n = len(self._desc)
         arr = (self._lib.EvalObj * n)(*self._desc)
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory()
+        self._box_at0 = C.sizeof(arr)                 # the box rows ride behind the descriptors in the same copy
+        raw = bytes(arr) + (bytes((self._lib.BoxRow * len(self._box))(*self._box)) if self._box else b"")
+        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
         self._host = host                   # (kept alive until the step's read-back has synchronised)
         self.desc = host.to(self.device, non_blocking=True)
 
@@ -145,8 +218,19 @@ class _DeviceOps:
         Wm = (max(o.W for o in objs) + 3) // 4 * 4
         self.ops.click_keys_batched(self._at(first), n, Hm, Wm, max(o.H * o.W for o in objs), self.device)
 
+    def boxes(self, rows, first, points_nd, n_batch, size, target_size, flag):
+        """Box prompts int32 [len(rows), 5] of the box rows from ``first`` on, on the device; ``flag``: index of the int32
+        behind the read-back records that reports a component table overflow."""
+        assert points_nd.shape[0] == len(rows) and all(n_obj <= n_batch for _, _, _, n_obj in rows)
+        flags = self.out[self.n_out:].view(torch.int32)
+        return self.ops.box_prompts_batched((self.desc, self._box_at0 + first * C.sizeof(self._lib.BoxRow)), len(rows),
+                                            points_nd.contiguous(), n_batch, size[0], size[1], _BOX_PRED_THRESH,
+                                            (flags, flag))
+
     def readback(self):
-        return self.out.cpu().numpy()       # the step's one synchronisation
+        out = self.out.cpu().numpy()        # the step's one synchronisation
+        self.flags = out[self.n_out:].view(np.int32).reshape(-1)      # (the box groups' overflow flags ride behind the records)
+        return out[:self.n_out]
 
 
 class _HostOps:
@@ -155,16 +239,25 @@ class _HostOps:
     def __init__(self, device):
         self.device = device
 
-    def begin(self, n_out):
-        self._desc = []
+    def begin(self, n_out, n_flags=0):
+        self._desc, self._box = [], []
         self.out = np.zeros((max(n_out, 1), 6), dtype=np.int64)
+        self.flags = np.zeros(n_flags, np.int32)
 
     def add(self, o, roi, src, out_row, prev=True):
         self._desc.append((o, tuple(roi), src, out_row, prev, o.clear_at))
         return len(self._desc) - 1
 
+    def add_box(self, o, roi, mirror, n_obj):
+        self._box.append((o, roi, mirror, n_obj))
+        return len(self._box) - 1
+
     def upload(self):
         pass
+
+    def boxes(self, rows, first, points_nd, n_batch, size, target_size, flag):
+        assert self._box[first:first + len(rows)] == list(rows)
+        return torch.from_numpy(_host_boxes(rows, points_nd, n_batch, size, target_size))
 
     @staticmethod
     def _resize(x, size):
@@ -217,9 +310,10 @@ class _HostOps:
 class BatchedEvaluator:
     """Runs ``evaluate_sample``'s loop (``evaluate_dataset``'s kwargs) over a stream of objects, ``batch_objects`` at a time."""
 
-    def __init__(self, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20):
-        assert batchable(predictor), "the predictor's transforms are not the batched path's (see batchable)"
-        self.pred, self.K = predictor, int(batch_objects)
+    def __init__(self, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20, as_prompt_type=0):
+        assert batchable(predictor, None, as_prompt_type), \
+            "the predictor's transforms or the prompt type are not the batched path's (see batchable)"
+        self.pred, self.K, self.prompt_type = predictor, int(batch_objects), int(as_prompt_type)
         self.max_iou_thr, self.pred_thr, self.min_clicks, self.max_clicks = max_iou_thr, pred_thr, min_clicks, max_clicks
         self.zoom = predictor.zoom_in
         self.flip = any(type(t) is AddHorizontalFlip for t in predictor.transforms)
@@ -262,6 +356,14 @@ class BatchedEvaluator:
             net_clicks = [c.copy(coords=roi.to_crop(c.coords, size)) for c in clicks]
             return roi, size, net_clicks, roi
         return whole, (o.H, o.W), list(clicks), (Roi(*o.roi) if o.roi is not None else whole)
+
+    def _own_rows(self, clicks):
+        """Rows per polarity of ``get_points_nd([clicks])``: the click layout the sequential call sees for this object."""
+        pos = sum(c.is_positive for c in clicks)
+        n = max(pos, len(clicks) - pos)
+        if self.pred.net_clicks_limit is not None:
+            n = min(self.pred.net_clicks_limit, n)
+        return max(1, n)
 
     def _wants_recalc(self, o):
         """ZoomIn.check_possible_recalculation after this step's prediction (o.box is its box)."""
@@ -313,7 +415,7 @@ class BatchedEvaluator:
         only computes them), plus the first click keys of the objects loaded into ``pending``."""
         stepping = [o for o in active if o.keys is not None]
         for o in stepping:
-            if not o.recalc:                            # Clicker.make_next_click
+            if not o.recalc and not o.host_box:         # Clicker.make_next_click
                 (fn_max, fn_at), (fp_max, fp_at) = (decode_key(k, o.W) for k in o.keys)
                 positive = fn_max > fp_max
                 at = fn_at if positive else fp_at
@@ -329,13 +431,28 @@ class BatchedEvaluator:
             new.append(o)
         key_objs = stepping + [o for o in active if o.keys is None] + new
         ops = self.ops
-        ops.begin(len(key_objs))
         row = {id(o): i for i, o in enumerate(key_objs)}
+        # size groups, split by prompt type: a click that ZoomIn re-runs goes through get_prediction, i.e. as clicks only.
+        # The box masks have the network's size except when a held roi meets an un-zoomed step (no prediction to zoom on):
+        # the sequential path then still crops them to target_size, so that size is part of the key
         groups = {}
         for o in stepping:
-            groups.setdefault(o.plan[1], []).append(o)
+            kind = 0 if o.recalc else self.prompt_type
+            box_size = None
+            if kind == 1:
+                box_size = tuple(self.zoom.target_size) if o.roi is not None else (o.H, o.W)
+            groups.setdefault((o.plan[1], kind, box_size, o.host_box), []).append(o)
+        n_flags = sum(1 for key in groups if key[1] == 1)
+        ops.begin(len(key_objs), n_flags)
         spans = []
-        for size, members in groups.items():
+        for (size, kind, box_size, host_box), members in groups.items():
+            bfirst, brows = None, []
+            if kind == 1:
+                for mirror in ((False, True) if self.flip else (False,)):
+                    for o in members:
+                        brows.append((o, o.roi, mirror, self._own_rows(o.clicks)))
+                        i = ops.add_box(*brows[-1])
+                        bfirst = i if bfirst is None else bfirst
             first = None
             for j, o in enumerate(members):
                 i = ops.add(o, o.plan[0], j, row[id(o)], prev=self.prev_channel)
@@ -344,19 +461,29 @@ class BatchedEvaluator:
             for j, o in enumerate(members):
                 i = ops.add(o, o.plan[3], j, row[id(o)])
                 pfirst = i if pfirst is None else pfirst
-            spans.append((size, members, first, pfirst))
+            spans.append((size, members, first, pfirst, kind, box_size, host_box, bfirst, brows))
         kfirst = None
         for o in key_objs:
             i = ops.add(o, Roi.whole(o.H, o.W), 0, row[id(o)])
             kfirst = i if kfirst is None else kfirst
         ops.upload()
-        for size, members, first, pfirst in spans:
+        flag_of, n_box = {}, 0
+        for size, members, first, pfirst, kind, box_size, host_box, bfirst, brows in spans:
             image_nd = ops.resize(members, first, len(members), size, self.flip, 4 if self.prev_channel else 3)
             lists = [o.plan[2] for o in members]
             if self.flip:
                 lists = lists + [[c.copy(coords=(c.coords[0], size[1] - c.coords[1] - 1)) for c in cl] for cl in lists]
             points_nd = self.pred.get_points_nd(lists).float()
-            logits = self.pred.net(image_nd, points_nd, (points_nd, None, None), 0)['instances']
+            boxes = None
+            if kind == 1:
+                n_batch, target = points_nd.shape[1] // 2, (self.zoom.target_size if self.zoom else None)
+                if host_box:
+                    boxes = torch.from_numpy(_host_boxes(brows, points_nd, n_batch, box_size, target)).to(self.device)
+                else:
+                    boxes = ops.boxes(brows, bfirst, points_nd, n_batch, box_size, target, n_box)
+                    flag_of.update((id(o), n_box) for o in members)
+                n_box += 1
+            logits = self.pred.net(image_nd, points_nd, (points_nd, boxes, None), kind)['instances']
             if tuple(logits.shape[2:]) != tuple(image_nd.shape[2:]):
                 from .transforms import resize_align_corners
                 logits = resize_align_corners(logits, image_nd.shape[2:])
@@ -367,10 +494,15 @@ class BatchedEvaluator:
         if key_objs:
             ops.keys(key_objs, kfirst, len(key_objs))
         out = ops.readback()
+        flags = ops.flags
         for o in key_objs:
             o.keys = (out[row[id(o)], 0], out[row[id(o)], 1])
             o.clear_at = -1
         for o in stepping:
+            if id(o) in flag_of and flags[flag_of[id(o)]]:
+                o.host_box = True                        # the component table overflowed: this forward is discarded and
+                continue                                 # the click repeated with boxes from the host code
+            o.host_box = False
             stats = out[row[id(o)], _STATS:].view(np.int32)
             o.box = tuple(int(v) for v in stats[2:7])       # ZoomIn._probs is the new prediction either way
             if self._wants_recalc(o):

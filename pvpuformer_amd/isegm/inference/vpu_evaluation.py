@@ -58,7 +58,7 @@ def _evaluate_sample(image, gt_mask, predictor, max_iou_thr, pred_thr, min_click
     return (clicker.clicks_list if clicker is not None else []), np.array(ious, dtype=np.float32), probs
 
 
-def evaluate_dataset(dataset, predictor, batch_objects=None, **kwargs):
+def evaluate_dataset(dataset, predictor, batch_objects=None, batch_box_prompts=None, **kwargs):
     """``dataset``: anything with ``len()`` and ``get_sample(i)`` returning an object with ``image``, ``objects_ids``
     and ``gt_mask(object_id)`` (the contract of the reference's isegm.data datasets).
 
@@ -66,11 +66,19 @@ def evaluate_dataset(dataset, predictor, batch_objects=None, **kwargs):
     objects at once, in lock-step through one batched forward per click (``batched.BatchedEvaluator``), and returns the
     same per-object IoU series in the same order.  That path applies only to a ``BasePredictor`` whose transforms are
     [ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip], without ``callback`` and with
-    ``as_prompt_type == 0``; in every other case the objects are silently evaluated one at a time, as with K = 1."""
+    click prompts (``as_prompt_type == 0``) or, when asked for, box prompts; in every other case the objects are silently
+    evaluated one at a time, as with K = 1.
+
+    ``batch_box_prompts`` (default: environment ``VPU_EVAL_BATCH_BOX`` = 1, else off): box prompts (``as_prompt_type == 1``)
+    take the batched path too, with the boxes derived on the device.  It is an opt-in because callers and tests rely on
+    box-prompt evaluation staying on the sequential loop by default."""
     if batch_objects is None:
         batch_objects = int(os.environ.get("VPU_EVAL_BATCH", "1") or 1)
-    if batch_objects > 1 and kwargs.get("max_clicks", 20) >= 1 and \
-            batched.batchable(predictor, kwargs.get("callback"), kwargs.get("as_prompt_type", 0)):
+    if batch_box_prompts is None:
+        batch_box_prompts = os.environ.get("VPU_EVAL_BATCH_BOX", "0") == "1"
+    ptype = kwargs.get("as_prompt_type", 0)
+    if batch_objects > 1 and kwargs.get("max_clicks", 20) >= 1 and (ptype == 0 or batch_box_prompts) and \
+            batched.batchable(predictor, kwargs.get("callback"), ptype):
         return _evaluate_dataset_batched(dataset, predictor, batch_objects, **kwargs)
     started = time.time()
     series = []
@@ -92,6 +100,7 @@ def dataset_objects(dataset):
 def _evaluate_dataset_batched(dataset, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20,
                               callback=None, as_prompt_type=0):
     started = time.time()
-    runner = batched.BatchedEvaluator(predictor, batch_objects, max_iou_thr, pred_thr, min_clicks, max_clicks)
+    runner = batched.BatchedEvaluator(predictor, batch_objects, max_iou_thr, pred_thr, min_clicks, max_clicks,
+                                      as_prompt_type=as_prompt_type)
     series = [ious for _, ious in runner.run(dataset_objects(dataset))]
     return series, time.time() - started

@@ -454,6 +454,25 @@ def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     _lib.call("vpu_click_keys_batched", ptr(objs), n, ptr(err), ptr(scratch), ptr(dist), Hm, Wm, max_hw, _stream())
 
 
+def box_prompts_batched(rows, n_rows, points, n_batch, S_h, S_w, pred_thresh, flag, kmax=None):
+    """Box prompts (x_center, y_center, width, height, slot) of n_rows rows (rows: device array of vpu_box_row) from their
+    previous prediction and ground truth -> int32 [n_rows, 5] on the device (vpu_box_prompts_batched).  points fp32 [n_rows,
+    2 * n_batch, 3] is the padded click layout the slot is expressed in; flag (one int32 on the device) becomes 1 when the
+    rows together have more than ``kmax`` components (default 1024 per row), and the boxes are then not valid."""
+    device = points.device
+    kmax = 1024 * n_rows if kmax is None else int(kmax)
+    assert points.dtype == torch.float32 and points.is_contiguous() and tuple(points.shape) == (n_rows, 2 * n_batch, 3)
+    masks = torch.empty(n_rows, S_h, S_w, device=device, dtype=torch.uint8)
+    counts = torch.empty(n_rows, 2, device=device, dtype=torch.int32)
+    roots = torch.empty(n_rows, S_h, S_w, device=device, dtype=torch.int32)
+    slots = torch.empty(n_rows, S_h, S_w, device=device, dtype=torch.int32)
+    table = torch.empty(6 * kmax + 1, device=device, dtype=torch.int32)
+    boxes = torch.empty(n_rows, 5, device=device, dtype=torch.int32)
+    _lib.call("vpu_box_prompts_batched", ptr(rows), n_rows, ptr(points), n_batch, S_h, S_w, float(pred_thresh), ptr(masks),
+              ptr(counts), ptr(roots), ptr(slots), ptr(table), kmax, ptr(boxes), ptr(flag), _stream())
+    return boxes
+
+
 def disk_maps(points, boxes, out, B, n, H, W, radius):
     _lib.call("vpu_disk_maps", ptr(points), ptr(boxes), ptr(out), B, n, H, W, float(radius), _stream())
 

@@ -2,8 +2,12 @@
 """Throughput of the NoBRS evaluation with K objects per forward (evaluate_dataset(batch_objects=K)): ViT-B/448 bf16,
 flip TTA, ZoomIn to 448 x 448 from the first click, a 20-click budget that no object stops early (max_iou_thr=2), over a
 synthetic set of objects on images of mixed sizes (448 x 448, 480 x 640, 375 x 500).  Prints one JSON line: object-clicks
-per second for each K, and the share of the time spent in the model forward (a second, synchronised pass).
-usage: python tools/bench_eval_batched.py [objects] [K ...]"""
+per second and milliseconds per click for each K, and the share of the time spent in the model forward (a second,
+synchronised pass).  K = 1 is the sequential loop (evaluate_sample per object).  ``--prompt-type 1`` evaluates with box
+prompts (BasePredictor.get_vqu_prediction derives the box per click sequentially, vpu_box_prompts_batched per step batched)
+and also counts, with the torch profiler, the device-to-host copies of a batched step (expected: exactly one).
+usage: python tools/bench_eval_batched.py [--prompt-type {0,1}] [objects] [K ...]"""
+import argparse
 import json
 import os
 import sys
@@ -47,24 +51,51 @@ class Dataset:
         return self.samples[i]
 
 
+def d2h_copies_per_step(run):
+    """(device-to-host copies, batched steps) of ``run()``, the copies counted from the profiler's memcpy events."""
+    from torch.profiler import ProfilerActivity, profile
+    from pvpuformer_amd.isegm.inference import batched
+    steps, orig = [], batched.BatchedEvaluator._step
+
+    def counted(self, *a, **k):
+        steps.append(1)
+        return orig(self, *a, **k)
+    batched.BatchedEvaluator._step = counted
+    try:
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            run()
+            torch.cuda.synchronize()
+    finally:
+        batched.BatchedEvaluator._step = orig
+    names = [e.name for e in prof.events() if "memcpy" in e.name.lower()]
+    if not any("htod" in n.lower().replace(" ", "") or "host -> device" in n.lower() for n in names):
+        return None, len(steps)              # the profiler reported no copies at all: nothing can be said
+    return sum(1 for n in names if "dtoh" in n.lower().replace(" ", "") or "device -> host" in n.lower()), len(steps)
+
+
 def main():
-    n_obj = int(sys.argv[1]) if len(sys.argv) > 1 else 32
-    ks = [int(k) for k in sys.argv[2:]] or [1, 4, 8, 16]
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--prompt-type", type=int, choices=(0, 1), default=0)
+    ap.add_argument("objects", nargs="?", type=int, default=32)
+    ap.add_argument("ks", nargs="*", type=int)
+    args = ap.parse_args()
+    n_obj, ks, ptype = args.objects, args.ks or [1, 4, 8, 16], args.prompt_type
     torch.manual_seed(0)
     model = VitMultiGaussianVector_ed_Model(**vitb_model_kwargs()).cuda()
     model.set_compute_dtype("bf16")
     model.eval()
     model.weights_frozen = True
     ds, warm = Dataset(n_obj), Dataset(max(ks) + 2)
-    kw = dict(max_iou_thr=2.0, pred_thr=0.49, max_clicks=20)
+    kw = dict(max_iou_thr=2.0, pred_thr=0.49, max_clicks=20, as_prompt_type=ptype)
     mk = lambda: get_predictor(model, "NoBRS", "cuda", with_flip=True,
                                zoom_in_params=dict(skip_clicks=-1, target_size=(448, 448)))
     res = {}
     for K in ks:
-        evaluate_dataset(warm, mk(), batch_objects=K, max_iou_thr=2.0, max_clicks=3)     # warm-up (kernels, shapes)
+        evaluate_dataset(warm, mk(), batch_objects=K, batch_box_prompts=True, max_iou_thr=2.0, max_clicks=3,
+                         as_prompt_type=ptype)     # warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        series, _ = evaluate_dataset(ds, mk(), batch_objects=K, **kw)
+        series, _ = evaluate_dataset(ds, mk(), batch_objects=K, batch_box_prompts=True, **kw)
         torch.cuda.synchronize()
         secs = time.perf_counter() - t0
         clicks = sum(len(s) for s in series)
@@ -80,17 +111,26 @@ def main():
         model.forward = timed
         try:
             t1 = time.perf_counter()
-            evaluate_dataset(ds, mk(), batch_objects=K, **kw)
+            evaluate_dataset(ds, mk(), batch_objects=K, batch_box_prompts=True, **kw)
             secs_sync = time.perf_counter() - t1
         finally:
             model.forward = orig
-        res[K] = dict(object_clicks_per_s=round(clicks / secs, 1), ms_per_step=round(secs / len(fwd) * 1e3, 2),
+        res[K] = dict(object_clicks_per_s=round(clicks / secs, 1), ms_per_click=round(secs / clicks * 1e3, 3),
+                      ms_per_step=round(secs / len(fwd) * 1e3, 2),
                       forwards=len(fwd), forward_share=round(sum(fwd) / secs_sync, 3), object_clicks=clicks)
     k1 = res.get(1, {}).get("object_clicks_per_s")
-    line = {"bench": "eval_batched", "model": "vitb448", "dtype": "bf16", "objects": n_obj, "max_clicks": 20,
+    line = {"bench": "eval_batched", "model": "vitb448", "dtype": "bf16", "objects": n_obj, "max_clicks": 20, "prompt_type": ptype,
             "results": {str(k): v for k, v in res.items()}}
     if k1:
         line["speedup_vs_k1"] = {str(k): round(v["object_clicks_per_s"] / k1, 2) for k, v in res.items()}
+    if 1 in res and len(res) > 1:
+        line["batched_over_sequential_ms_per_click"] = {str(k): round(v["ms_per_click"] / res[1]["ms_per_click"], 3)
+                                                        for k, v in res.items() if k != 1}
+    if ptype == 1 and max(ks) > 1:
+        copies, steps = d2h_copies_per_step(
+            lambda: evaluate_dataset(warm, mk(), batch_objects=max(ks), batch_box_prompts=True, max_iou_thr=2.0, max_clicks=4,
+                                     as_prompt_type=1))
+        line["batched_step_d2h_copies"] = {"K": max(ks), "steps": steps, "device_to_host_copies": copies}
     print(json.dumps(line))
 
 
