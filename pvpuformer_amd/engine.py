@@ -15,7 +15,9 @@ Composes the C-ABI kernels (``include/vpu_hip.h``) into the model of
 """
 import contextlib
 import math
+import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -141,7 +143,6 @@ class Engine:
         self.training = False
         self.shadow_valid = False
         self._const_ready = False
-        import os
         self.use_flash = True    # False: the unfused S / P path (what fp32 and other head dimensions take anyway); an attribute, no environment knob
         # weight gradients are only consumed by the optimizer: VPU_WGRAD_STREAM=1 runs them on a second HIP stream.  Off by
         # default: since the GEMM launches became persistent (every launch fills the chip) the two streams only share the
@@ -189,14 +190,10 @@ class Engine:
         # end of backward with the chip a quarter full (0.47 ms per step).
         self.unify_wgrad = True
         self.lazy_zero = True      # zero_grad(lazy=True) honoured
-        # round 5 launch fusions (the three gates in one launch per pass, the derived operands in one batched cast, the q_out
-        # gradient fan-out in one launch, conv_seg's partial sums through the batched column sums): ``r5_fused`` = False runs the
-        # round-4 launches instead (same-box A/B runs)
-        self.r5_fused = True
         # split launches of the neck's prompt<->image attentions (cross_attention): ranges per long side; 1 = off
         self.xattn_split = max(1, int(os.environ.get("VPU_XATTN_SPLIT", "1")))
         # round 5: the DMA neck's prompt-token chain (~90 dependent launches of <= 108 workgroups each) on its own HIP stream
-        # beside the image-side launches (Engine._neck_lanes); VPU_NECK_LANES=0 = everything on the caller's stream
+        # beside the image-side launches (Engine._neck_two_lane); VPU_NECK_LANES=0 = everything on the caller's stream
         self.neck_lanes = int(os.environ.get("VPU_NECK_LANES", "0"))     # (2: only the part that runs beside the backbone)
         self._tok_stream = None
         self._in_lanes = False    # backward is inside the two-lane section: the weight-gradient queue only collects
@@ -272,17 +269,6 @@ class Engine:
             ops.cast2d(self.flat, self.total, self.shadow, self.total, 1, self.total)
         k3 = 3 * P * P
         po = self.names["backbone.pos_embed"][0]
-        if not self.r5_fused:
-            ops.cast2d(self.Pm("backbone.patch_embed.proj.weight"), k3, (self.w_patch, 0), 2 * self.k3p, D, k3)
-            ops.cast2d(self.Pm("patch_embed_coords.proj.weight"), k3, (self.w_patch, self.k3p), 2 * self.k3p, D, k3)
-            ops.add4(self.Pm("backbone.patch_embed.proj.bias"), self.Pm("patch_embed_coords.proj.bias"), None, None, self.b_patch, D)
-            ops.cast2d(self.Pm("neck.ffn_layer.lin1.weight"), self.E, self.w_lin1p, self.Epad, 2048, self.E, self.Epad)
-            tmp = torch.empty(self.NT, D, device=self.dev, dtype=self.td)
-            ops.cast2d((self.flat, po + D), D, tmp, D, self.NT, D)
-            ops.window_permute(tmp, self.pos_win, 1, self.g, self.wside, D, to_raster=False)
-            self._pos_cache = {(self.g, self.wside): self.pos_win}
-            self.shadow_valid = True
-            return
         # the derived operands in ONE launch (round 5: vpu_cast2d_batched; five launches before): the two patch embeddings side
         # by side in the fused weight, the sum of their biases, the K-padded PuE weight, pos_embed[:, 1:] in window order
         ops.cast2d_batched([
@@ -433,14 +419,6 @@ class Engine:
         else:
             ops.colsum_f32(part.view(nrows, 2 * Cdim)[:, :Cdim].contiguous(), self.G(prefix + ".weight"), nrows, Cdim, beta=1.0)
             ops.colsum_f32(part.view(nrows, 2 * Cdim)[:, Cdim:].contiguous(), self.G(prefix + ".bias"), nrows, Cdim, beta=1.0)
-
-    def _convseg_sums(self, part, part_b, nb, Cc):
-        if self.r5_fused:
-            self._csq.append((part, self.G("head.conv_seg.weight"), nb, Cc))
-            self._csq.append((part_b, self.G("head.conv_seg.bias"), nb, 1))
-        else:
-            ops.colsum_f32(part, self.G("head.conv_seg.weight"), nb, Cc, beta=1.0)
-            ops.colsum_f32(part_b, self.G("head.conv_seg.bias"), nb, 1, beta=1.0)
 
     def _colsum_to(self, dy, ld, gname, rows, N):
         part = self._new(64, N, dtype=torch.float32)
@@ -863,25 +841,35 @@ class Engine:
             self.tape.append(bwd)
         return y
 
-    def mha(self, prefix, xq, xk, xv, B, nq, nk, internal, resid=None):
-        """transformer.py Attention.forward (:499-521) + optional residual of the caller."""
-        D, H = self.D, 8
-        hd = internal // H
-        # the three projections are independent: their forward GEMMs -- and, in backward, their dgrads -- are queued and
-        # launched together (the 576-row ones in ONE grouped launch instead of a split-K GEMM + reduce each)
+    def _group(self, fn):
+        """The projections queued by fn() leave in one grouped launch; so do their dgrads in backward (the 576-row ones in ONE
+        grouped launch instead of a split-K GEMM + reduce each)."""
         if self.training:
-            self.tape.append(self.flush_group)       # runs AFTER the three backward closures below
-        Qp = self.linear(xq, prefix + ".q_proj.weight", prefix + ".q_proj.bias", B * nq, internal, D, group=True)
-        Kp = self.linear(xk, prefix + ".k_proj.weight", prefix + ".k_proj.bias", B * nk, internal, D, group=True)
-        Vp = self.linear(xv, prefix + ".v_proj.weight", prefix + ".v_proj.bias", B * nk, internal, D, group=True)
+            self.tape.append(self.flush_group)       # runs AFTER the backward closures fn() records
+        r = fn()
         self.flush_group()
-        O = Var(self._new(B * nq, internal))
+        return r
+
+    def _proj(self, prefix, which, x, rows, width):
+        return self.linear(x, f"{prefix}.{which}_proj.weight", f"{prefix}.{which}_proj.bias", rows, width, self.D, group=True)
+
+    def _attend(self, B, prefix, Qp, Kp, Vp, nq, nk, width, resid):
+        """Attention of the projected Qp / Kp / Vp (8 heads) and the output projection [+ resid]."""
+        H, hd = 8, width // 8
+        O = Var(self._new(B * nq, width))
         if self.dt == BF16 and self.use_flash and hd % 16 == 0 and hd <= 128:
-            self.cross_attention(Qp, Kp, Vp, O, B, H, nq, nk, hd, internal, 1.0 / math.sqrt(hd))
+            self.cross_attention(Qp, Kp, Vp, O, B, H, nq, nk, hd, width, 1.0 / math.sqrt(hd))
         else:
-            self.sdpa((Qp, 0, internal, nq), (Kp, 0, internal, nk), (Vp, 0, internal, nk), (O, 0, internal, nq), B, H,
-                      nq, nk, hd, 1.0 / math.sqrt(hd))
-        return self.linear(O, prefix + ".out_proj.weight", prefix + ".out_proj.bias", B * nq, D, internal, resid=resid)
+            self.sdpa((Qp, 0, width, nq), (Kp, 0, width, nk), (Vp, 0, width, nk), (O, 0, width, nq), B, H, nq, nk, hd,
+                      1.0 / math.sqrt(hd))
+        return self.linear(O, prefix + ".out_proj.weight", prefix + ".out_proj.bias", B * nq, self.D, width, resid=resid)
+
+    def mha(self, prefix, xq, xk, xv, B, nq, nk, internal, resid=None):
+        """transformer.py Attention.forward (:499-521) + optional residual of the caller: the three independent projections in
+        one group, then ``_attend``."""
+        Qp, Kp, Vp = self._group(lambda: (self._proj(prefix, "q", xq, B * nq, internal), self._proj(prefix, "k", xk, B * nk, internal),
+                                          self._proj(prefix, "v", xv, B * nk, internal)))
+        return self._attend(B, prefix, Qp, Kp, Vp, nq, nk, internal, resid)
 
     def groupnorm(self, x, prefix, B, HW, Cdim, gelu):
         y = Var(torch.empty_like(x.t))
@@ -1000,105 +988,65 @@ class Engine:
         if not self.shadow_valid:
             self.refresh_weights()
         self.training = training
-        self.tape = Tape()
-        tape = self.tape
-        c = self.cfg
+        self.tape = Tape()        # replaced here only: the stages record on it (the token lane swaps its ``fns`` temporarily)
         B, H, W_ = image4.shape[0], image4.shape[2], image4.shape[3]
-        D, P, heads = self.D, self.P, self.heads
+        D = self.D
         # the token grid follows the INPUT (the prompt vectors keep the constructor's image size, as in the reference:
         # is_vpu_model.py:189-230 builds them from self.image_size)
         # (window_geometry: any square size the reference's patchify accepts; the grid is floored when H % P != 0 and the
         # last H % P pixel rows / columns are read by nothing but the final upsample's output shape)
         check_square(H, W_)
-        g, nw_side, wside = window_geometry(H, P)
+        g, nw_side, wside = window_geometry(H, self.P)
         NT = g * g
         pos_win, kpe_tab = self._pos_for(g, wside), self._kpe_for(g)
-        M = B * NT
-        self._token_rows = M          # the reduction length of the ViT blocks' weight gradients (the packed queue)
+        self._token_rows = B * NT     # the reduction length of the ViT blocks' weight gradients (the packed queue)
         n = points.shape[1] // 2
         points = self._upload(points, torch.float32)
-        use_box = prompt_type == 1
-        if use_box:
-            boxes = self._upload(boxes, torch.int32)
-        use_scr = prompt_type == 2
-        if use_scr:
+        boxes = self._upload(boxes, torch.int32) if prompt_type == 1 else None
+        curve = prof = None
+        if prompt_type == 2:
             curve = self._upload(scribble[0], torch.int32)
             prof = self._upload(scribble[1], torch.float64)
             assert curve.shape[0] == B and tuple(prof.shape) == (B, 2 * self.img)
-        nq = 2 * self.nmax
-        # round 5, two lanes: the prompt tokens' side of the DMA neck on its own stream (see the neck below).  What needs the
+        prompts = (points, boxes, curve, prof)
+        # round 5, two lanes: the prompt tokens' side of the DMA neck on its own stream (_neck_two_lane).  What needs the
         # prompts only -- the PuE vectors, their MLP, layer 0's token self-attention -- is launched now, beside the backbone;
         # its backward closures are kept aside and join the tape at the neck's place (they belong to the neck's gradient range)
         lanes = (self.neck_lanes and training and self.dt == BF16 and self.use_flash and not self.use_side and self.fuse_ln_pe
                  and (D // 2 // 8) % 16 == 0 and D // 8 <= 128)
-        T = None
+        if lanes and self._tok_stream is None:
+            self._tok_stream = torch.cuda.Stream(device=self.dev)
+        cx = SimpleNamespace(B=B, H=H, W=W_, g=g, wside=wside, nw_side=nw_side, NT=NT, M=B * NT, n=n, nq=2 * self.nmax,
+                             training=training, taps=taps, T=self._tok_stream if lanes else None)
+        started = self._start_token_lane(cx, prompts) if lanes and self.neck_lanes != 3 else None
+        x = self._embed(cx, image4, prompts, pos_win, coord_override, prenorm)
+        xr = self._blocks(cx, x)
         if lanes:
-            if self._tok_stream is None:
-                self._tok_stream = torch.cuda.Stream(device=self.dev)
-            T = self._tok_stream
-        tok = lambda: self._lane(T)
+            q0, hs = self._neck_two_lane(cx, prompts, xr, kpe_tab, started)
+        else:
+            q0, hs = self._neck(cx, prompts, xr, kpe_tab)
+        q_out, maps = self._gates(cx, xr, q0, hs)
+        feats = self._fpn(cx, maps)
+        inst, aux = self._head(cx, feats, q_out, drop_mask, materialize_aux)
+        self.last_tape = self.tape if training else None
+        return inst, aux
 
-        def group(fn):      # the projections queued by fn() leave in one grouped launch; so do their dgrads (backward)
-            if training:
-                self.tape.append(self.flush_group)
-            r = fn()
-            self.flush_group()
-            return r
-
-        def proj(prefix, which, x_, rows, width):
-            return self.linear(x_, f"{prefix}.{which}_proj.weight", f"{prefix}.{which}_proj.bias", rows, width, D, group=True)
-
-        def attend(prefix, Qp, Kp, Vp, nq_, nk_, width, resid):
-            O_ = Var(self._new(B * nq_, width))
-            self.cross_attention(Qp, Kp, Vp, O_, B, 8, nq_, nk_, width // 8, width, 1.0 / math.sqrt(width // 8))
-            return self.linear(O_, prefix + ".out_proj.weight", prefix + ".out_proj.bias", B * nq_, D, width, resid=resid)
-
-        def prompt_vectors():
-            pue_ = Var(self._new(B * nq, self.Epad))
-            ops.pue_encode(points, boxes if use_box else None, self.lut, pue_.t, None, B, n, self.nmax, self.img, self.Epad)
-            if use_scr:     # _guassinvector_scribble (is_vpu_model.py:294-352): the last valid positive row becomes the scribble
-                ops.pue_scribble_rows(points, prof, pue_.t, None, B, n, self.nmax, self.img, self.Epad)
-            return self.mlp(pue_, "neck.ffn_layer.lin1", "neck.ffn_layer.lin2", B * nq, self.Epad, 2048, D, "relu",
-                            w1=self.w_lin1p, k_grad=self.E, x_grad=False)
-
-        def tok_pre(l, q_, qq_, q0_):      # token side of layer l up to the token -> image queries: needs no image token
-            p_ = f"neck.att.layers.{l}"
-            if l == 0:
-                q_ = self.mha(p_ + ".self_attn", q_, q_, q_, B, nq, nq, D)
-            else:
-                q_ = self.mha(p_ + ".self_attn", qq_, qq_, q_, B, nq, nq, D, resid=q_)
-            q_, qq_ = self.layernorm(q_, p_ + ".norm1", B * nq, D, 1e-5, pe=q0_.t, pe_rows=B * nq, pe_var=q0_)
-            Qt_ = group(lambda: proj(p_ + ".cross_attn_token_to_image", "q", qq_, B * nq, D // 2))
-            return q_, qq_, Qt_
-
-        def start_token_lane():
-            fns_main, self.tape.fns = self.tape.fns, []
-
-            def lanes_done():       # (backward leaves the two-lane section: what the queue collected meanwhile may go)
-                self._in_lanes = False
-                for kind in sorted({0 if e[3] <= 2048 else e[3] for e in self._wq}):
-                    self._wgrad_autoflush(kind)
-            h_fork = self._xrec(None, on_bwd=lanes_done)
-            self._xwait(h_fork, T)
-            with tok():
-                q0_ = prompt_vectors()
-                pre_ = tok_pre(0, q0_, None, q0_)
-            early_, self.tape.fns = self.tape.fns, fns_main
-            return early_, q0_, pre_
-
-        if lanes and self.neck_lanes != 3:
-            early, q0, q_pre = start_token_lane()
-        # ---- a1-a4: prompts -> coordinate features -> fused patch embedding (window token order)
+    # The stages of ``forward``, in order.  ``cx`` holds the shape scalars of the call (a plain namespace); everything else a
+    # stage reads is an argument, and its backward closures close over its own values only.
+    def _embed(self, cx, image4, prompts, pos_win, coord_override, prenorm):
+        """a1-a4: prompts -> coordinate features -> fused patch embedding; returns the tokens x (window order)."""
+        B, H, W_, g, wside, NT, M, D, P = cx.B, cx.H, cx.W, cx.g, cx.wside, cx.NT, cx.M, self.D, self.P
+        points, boxes, curve, _ = prompts
         if coord_override is not None:
             disks = coord_override.to(device=self.dev, dtype=torch.float32).contiguous()
             assert tuple(disks.shape) == (B, 2, H, W_)
         else:
             disks = self._new(B, 2, H, W_, dtype=torch.float32)
-            ops.disk_maps(points, boxes if use_box else None, disks, B, n, H, W_, self.norm_radius)
-            if use_scr:     # ISModel.draw_scribble (is_model.py:123-146): poly-line into the positive channel
+            ops.disk_maps(points, boxes, disks, B, cx.n, H, W_, self.norm_radius)
+            if curve is not None:     # ISModel.draw_scribble (is_model.py:123-146): poly-line into the positive channel
                 ops.draw_polyline(curve, disks, B, curve.shape[1], H, W_)
-        if taps is not None:
-            taps["disks"] = disks
+        if cx.taps is not None:
+            cx.taps["disks"] = disks
         KP = 2 * self.k3p
         cols = self._new(M, KP)
         if H % P == 0:
@@ -1108,18 +1056,16 @@ class Engine:
         x = Var(self._new(M, D))
         ops.gemm(cols, self.w_patch, x.t, M, D, KP, KP, KP, D, self.dt,
                  flags=EPI_BIAS | EPI_RESID, bias=self.b_patch, resid=pos_win, ldr=D, resid_period=NT)
-        if training:
-            x0 = x
-
+        if cx.training:
             def bwd_patch():
-                if x0.g is None:
+                if x.g is None:
                     return
                 k3 = 3 * P * P
                 for nm, co in (("backbone.patch_embed.proj", 0), ("patch_embed_coords.proj", self.k3p)):
-                    self._wgrad(x0.g, D, (cols, co), KP, nm + ".weight", D, k3, M, bias=nm + ".bias")
+                    self._wgrad(x.g, D, (cols, co), KP, nm + ".weight", D, k3, M, bias=nm + ".bias")
                 # pos_embed[:, 1:] gradient: sum over the batch, back to raster order
                 s = self._new(NT * D, dtype=torch.float32)
-                ops.colsum(x0.g, NT * D, s, None, B, NT * D, beta=0.0)   # rows = B <= 64: single-pass kernel
+                ops.colsum(x.g, NT * D, s, None, B, NT * D, beta=0.0)   # rows = B <= 64: single-pass kernel
                 r = self._new(NT * D, dtype=torch.float32)
                 ops.window_permute(s, r, 1, g, wside, D, to_raster=True)
                 gp = (self.gflat, self.names["backbone.pos_embed"][0] + D)
@@ -1129,20 +1075,22 @@ class Engine:
                     # another input size: the tokens saw the bicubic re-gridding of pos_embed (pos_embed.py:99-128), a fixed
                     # linear map R of the g0 x g0 grid onto the g x g one; its adjoint takes the gradient back:
                     # d pos[g0^2, D] += R^T[g0^2, g^2] . d regridded[g^2, D]   (exact-fp32 GEMM into the flat gradient buffer)
-                    g0 = self.g
-                    ops.gemm(self._regrid_adjoint(g), r, gp, g0 * g0, D, NT, NT, D, D, F32, transB=True,
+                    ops.gemm(self._regrid_adjoint(g), r, gp, self.g * self.g, D, NT, NT, D, D, F32, transB=True,
                              flags=EPI_OUT_F32 | EPI_ACCUM)
             self.tape.append(bwd_patch)
-        if taps is not None:
-            taps["tokens0_win"] = x.t
-        # ---- a5/a6: ViT blocks on window-ordered tokens
+        if cx.taps is not None:
+            cx.taps["tokens0_win"] = x.t
+        return x
+
+    def _blocks(self, cx, x):
+        """a5/a6: the ViT blocks on window-ordered tokens, then the un-permute; returns the raster-order tokens xr."""
+        B, g, wside, NT, M, D, heads = cx.B, cx.g, cx.wside, cx.NT, cx.M, self.D, self.heads
         hd = D // heads
         for i in range(1, self.depth + 1):
-            if training:
+            if cx.training:
                 self._mark_ready(f"backbone.blocks.{i - 1}.norm1.weight",
                                  f"backbone.blocks.{i}.norm1.weight" if i < self.depth else "backbone.fc_norm.weight")
-            is_global = (i % self.group) == 0
-            nwin = 1 if is_global else nw_side * nw_side
+            nwin = 1 if i % self.group == 0 else cx.nw_side * cx.nw_side      # (every ``group``-th block is global)
             nt = NT // nwin
             p = f"backbone.blocks.{i - 1}."
             h1 = self.layernorm(x, p + "norm1", M, D, 1e-6)
@@ -1155,120 +1103,162 @@ class Engine:
                           heads, nt, nt, hd, hd ** -0.5)
             x1 = self.linear(O, p + "attn.proj.weight", p + "attn.proj.bias", M, D, D, resid=x)
             h2 = self.layernorm(x1, p + "norm2", M, D, 1e-6)
-            x = self.mlp(h2, p + "mlp.fc1", p + "mlp.fc2", M, D, D * c["mlp_ratio"], D, "gelu", resid=x1)
+            x = self.mlp(h2, p + "mlp.fc1", p + "mlp.fc2", M, D, D * self.cfg["mlp_ratio"], D, "gelu", resid=x1)
         xr = Var(self._new(M, D))
         ops.window_permute(x.t, xr.t, B, g, wside, D, to_raster=True)
-        if training:
-            xw = x
-
+        if cx.training:
             def bwd_perm():
                 if xr.g is None:
                     return
                 gw = torch.empty_like(xr.g)
                 ops.window_permute(xr.g, gw, B, g, wside, D, to_raster=False)
-                self.acc(xw, gw, take=True)
+                self.acc(x, gw, take=True)
             self.tape.append(bwd_perm)
-        if taps is not None:
-            taps["backbone"] = xr.t
-        if training:
+        if cx.taps is not None:
+            cx.taps["backbone"] = xr.t
+        if cx.training:
             self._mark_ready("backbone.fc_norm.weight", None)  # neck + head + the unused tail: final once they are done
-        # ---- a7/a8: PuE vectors, a10/a11: DMA neck
-        nQ, nK = B * nq * D, M * D
-        hs = []
-        if lanes:
-            # Two lanes.  The neck alternates between the 576 prompt tokens (self-attention, LayerNorms, MLP, their projections:
-            # ~30 launches per layer of <= 108 workgroups, latency-bound) and the 9408 image tokens (projections, LayerNorm:
-            # full-chip launches).  One stream serialises them; here the token side runs on its own stream and meets the image
-            # side at the two attentions of a layer only:
-            #   image lane (the caller's stream): K / V of tokens -> image, Q of image -> tokens | ... | image -> tokens, norm4
-            #   token lane:  self-attention, norm1, Q | tokens -> image, norm2, MLP, norm3, K / V  | next layer's self-attention ..
-            # Events order the crossings (_xrec / _xwait; their backward closures mirror them), the backward closures run on the
-            # lane they were recorded on, and the weight-gradient queue only collects while backward is inside (its launches
-            # read operands of both lanes).  Same kernels on the same operands: the results do not depend on the lanes.
-            if self.neck_lanes == 3:      # (3: the token lane starts here, nothing runs beside the backbone)
-                early, q0, q_pre = start_token_lane()
-            self.tape.fns.extend(early)
-            if self.neck_lanes == 2:      # the token lane ends here: the neck itself on the caller's stream
-                h_early = self._xrec(T)
-                self._xwait(h_early, None)
-                T = None
-            k = xr
-            kk = self.add_pe(k, kpe_tab, nK, NT * D)
-            q, qq, Qt = q_pre
-            for l in range(4):          # (l == 3: final_attn_token_to_image)
-                p = f"neck.att.layers.{l}"
-                t2i = p + ".cross_attn_token_to_image" if l < 3 else "neck.att.final_attn_token_to_image"
-                i2t = p + ".cross_attn_image_to_token"
-                Kt, Vt = group(lambda: (proj(t2i, "k", kk, M, D // 2), proj(t2i, "v", k, M, D // 2)))
-                h_kv = self._xrec(None)
-                if l < 3:
-                    Qi = group(lambda: proj(i2t, "q", kk, M, D // 2))
-                with tok():
-                    if l == 3:
-                        Qt = group(lambda: proj(t2i, "q", qq, B * nq, D // 2))
-                    elif l > 0:
-                        q, qq, Qt = tok_pre(l, q, qq, q0)
-                self._xwait(h_kv, T)
-                with tok():
-                    q = attend(t2i, Qt, Kt, Vt, nq, NT, D // 2, q)
-                    if l == 3:
-                        q = self.layernorm(q, "neck.att.norm_final_attn", B * nq, D, 1e-5)
-                    else:
-                        q = self.layernorm(q, p + ".norm2", B * nq, D, 1e-5)
-                        q = self.mlp(q, p + ".mlp.lin1", p + ".mlp.lin2", B * nq, D, 1024, D, "relu", resid=q)
-                        q, qq = self.layernorm(q, p + ".norm3", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
-                        Ki, Vi = group(lambda: (proj(i2t, "k", qq, B * nq, D // 2), proj(i2t, "v", q, B * nq, D // 2)))
-                if l == 3:
-                    break
-                h_tok = self._xrec(T)
-                self._xwait(h_tok, None)
-                k2 = attend(i2t, Qi, Ki, Vi, NT, nq, D // 2, k)
-                k, kk = self.layernorm(k2, p + ".norm4", M, D, 1e-5, pe=kpe_tab, pe_rows=NT)
-                if l != 2:
-                    hs.append((q, k))
-            hs.append((q, k))
+        return xr
 
-            def lanes_begin():
-                self._in_lanes = True
-            h_join = self._xrec(T)
-            self._xwait(h_join, None, on_bwd=lanes_begin)
+    def _prompt_vectors(self, cx, prompts):
+        """a7/a8: the PuE vectors and their MLP; returns the prompt tokens q0."""
+        B, n, nq = cx.B, cx.n, cx.nq
+        points, boxes, _, prof = prompts
+        pue = Var(self._new(B * nq, self.Epad))
+        ops.pue_encode(points, boxes, self.lut, pue.t, None, B, n, self.nmax, self.img, self.Epad)
+        if prof is not None:     # _guassinvector_scribble (is_vpu_model.py:294-352): the last valid positive row becomes the scribble
+            ops.pue_scribble_rows(points, prof, pue.t, None, B, n, self.nmax, self.img, self.Epad)
+        return self.mlp(pue, "neck.ffn_layer.lin1", "neck.ffn_layer.lin2", B * nq, self.Epad, 2048, self.D, "relu",
+                        w1=self.w_lin1p, k_grad=self.E, x_grad=False)
+
+    def _neck_layer_tokens(self, cx, l, q, qq, q0):
+        """Head of neck layer l, needs no image token: token self-attention and norm1; returns (q, q + q0)."""
+        # queries + query_pe / keys + key_pe (transformer.py:439-457) come out of the LayerNorm launch that produces the
+        # queries / keys (Engine.layernorm(pe=...)); the sum of unchanged queries is taken once -- the reference adds it
+        # again at the next layer's start (:439 after :457, :374 after :457): same numbers
+        B, nq, D, p = cx.B, cx.nq, self.D, f"neck.att.layers.{l}"
+        if l == 0:
+            q = self.mha(p + ".self_attn", q, q, q, B, nq, nq, D)
         else:
-            q0 = prompt_vectors()
-            q, k = q0, xr
-            qq = None
-            kk = self.add_pe(k, kpe_tab, nK, NT * D)
-            for l in range(3):
-                p = f"neck.att.layers.{l}"
-                # queries + query_pe / keys + key_pe (transformer.py:439-457) come out of the LayerNorm launch that produces the
-                # queries / keys (Engine.layernorm(pe=...)); the sum of unchanged queries is taken once -- the reference adds it
-                # again at the next layer's start (:439 after :457, :374 after :457): same numbers
-                if l == 0:
-                    q = self.mha(p + ".self_attn", q, q, q, B, nq, nq, D)
+            q = self.mha(p + ".self_attn", qq, qq, q, B, nq, nq, D, resid=q)
+        return self.layernorm(q, p + ".norm1", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
+
+    def _neck(self, cx, prompts, xr, kpe_tab):
+        """a10/a11: the DMA neck on the caller's stream; returns (q0, hs), hs = the three (queries, keys) pairs of the gates."""
+        B, NT, M, nq, D = cx.B, cx.NT, cx.M, cx.nq, self.D
+        q0 = self._prompt_vectors(cx, prompts)
+        q, k, qq, hs = q0, xr, None, []
+        kk = self.add_pe(k, kpe_tab, M * D, NT * D)
+        for l in range(3):
+            p = f"neck.att.layers.{l}"
+            q, qq = self._neck_layer_tokens(cx, l, q, qq, q0)
+            q = self.mha(p + ".cross_attn_token_to_image", qq, kk, k, B, nq, NT, D // 2, resid=q)
+            q = self.layernorm(q, p + ".norm2", B * nq, D, 1e-5)
+            q = self.mlp(q, p + ".mlp.lin1", p + ".mlp.lin2", B * nq, D, 1024, D, "relu", resid=q)
+            q, qq = self.layernorm(q, p + ".norm3", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
+            k2 = self.mha(p + ".cross_attn_image_to_token", kk, qq, q, B, NT, nq, D // 2, resid=k)
+            k, kk = self.layernorm(k2, p + ".norm4", M, D, 1e-5, pe=kpe_tab, pe_rows=NT)
+            if l != 2:
+                hs.append((q, k))
+        q = self.mha("neck.att.final_attn_token_to_image", qq, kk, k, B, nq, NT, D // 2, resid=q)
+        q = self.layernorm(q, "neck.att.norm_final_attn", B * nq, D, 1e-5)
+        hs.append((q, k))
+        return q0, hs
+
+    def _start_token_lane(self, cx, prompts):
+        """Two-lane neck, the part that needs the prompts only, on the token stream: PuE vectors, layer 0's token head and its
+        token -> image queries.  Returns (early, q0, (q, qq, Qt)): ``early`` = the backward closures recorded here, kept off
+        the tape until ``_neck_two_lane`` splices them in at the neck's place."""
+        T = cx.T
+        fns_main, self.tape.fns = self.tape.fns, []
+
+        def lanes_done():       # (backward leaves the two-lane section: what the queue collected meanwhile may go)
+            self._in_lanes = False
+            for kind in sorted({0 if e[3] <= 2048 else e[3] for e in self._wq}):
+                self._wgrad_autoflush(kind)
+        h_fork = self._xrec(None, on_bwd=lanes_done)
+        self._xwait(h_fork, T)
+        with self._lane(T):
+            q0 = self._prompt_vectors(cx, prompts)
+            q, qq = self._neck_layer_tokens(cx, 0, q0, None, q0)
+            Qt = self._group(lambda: self._proj("neck.att.layers.0.cross_attn_token_to_image", "q", qq, cx.B * cx.nq, self.D // 2))
+        early, self.tape.fns = self.tape.fns, fns_main
+        return early, q0, (q, qq, Qt)
+
+    def _neck_two_lane(self, cx, prompts, xr, kpe_tab, started):
+        """a10/a11 on two lanes (``neck_lanes``); ``started``: what ``_start_token_lane`` returned beside the backbone, None =
+        the token lane starts here.  Returns (q0, hs) like ``_neck``.
+        The neck alternates between the 576 prompt tokens (self-attention, LayerNorms, MLP, their projections: ~30 launches
+        per layer of <= 108 workgroups, latency-bound) and the 9408 image tokens (projections, LayerNorm: full-chip launches).
+        One stream serialises them; here the token side runs on its own stream and meets the image side at the two attentions
+        of a layer only:
+          image lane (the caller's stream): K / V of tokens -> image, Q of image -> tokens | ... | image -> tokens, norm4
+          token lane:  self-attention, norm1, Q | tokens -> image, norm2, MLP, norm3, K / V  | next layer's self-attention ..
+        Events order the crossings (_xrec / _xwait; their backward closures mirror them), the backward closures run on the
+        lane they were recorded on, and the weight-gradient queue only collects while backward is inside (its launches read
+        operands of both lanes).  Same kernels on the same operands: the results do not depend on the lanes."""
+        B, NT, M, nq, D, T = cx.B, cx.NT, cx.M, cx.nq, self.D, cx.T
+        group, proj = self._group, self._proj
+        if started is None:           # (neck_lanes == 3: nothing ran beside the backbone)
+            started = self._start_token_lane(cx, prompts)
+        early, q0, (q, qq, Qt) = started
+        self.tape.fns.extend(early)
+        if self.neck_lanes == 2:      # the token lane ends here: the neck itself on the caller's stream
+            h_early = self._xrec(T)
+            self._xwait(h_early, None)
+            T = None
+        k, hs = xr, []
+        kk = self.add_pe(k, kpe_tab, M * D, NT * D)
+        for l in range(4):          # (l == 3: final_attn_token_to_image)
+            p = f"neck.att.layers.{l}"
+            t2i = p + ".cross_attn_token_to_image" if l < 3 else "neck.att.final_attn_token_to_image"
+            i2t = p + ".cross_attn_image_to_token"
+            Kt, Vt = group(lambda: (proj(t2i, "k", kk, M, D // 2), proj(t2i, "v", k, M, D // 2)))
+            h_kv = self._xrec(None)
+            if l < 3:
+                Qi = group(lambda: proj(i2t, "q", kk, M, D // 2))
+            with self._lane(T):
+                if 0 < l < 3:
+                    q, qq = self._neck_layer_tokens(cx, l, q, qq, q0)
+                if l > 0:
+                    Qt = group(lambda: proj(t2i, "q", qq, B * nq, D // 2))
+            self._xwait(h_kv, T)
+            with self._lane(T):
+                q = self._attend(B, t2i, Qt, Kt, Vt, nq, NT, D // 2, q)
+                if l == 3:
+                    q = self.layernorm(q, "neck.att.norm_final_attn", B * nq, D, 1e-5)
                 else:
-                    q = self.mha(p + ".self_attn", qq, qq, q, B, nq, nq, D, resid=q)
-                q, qq = self.layernorm(q, p + ".norm1", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
-                q = self.mha(p + ".cross_attn_token_to_image", qq, kk, k, B, nq, NT, D // 2, resid=q)
-                q = self.layernorm(q, p + ".norm2", B * nq, D, 1e-5)
-                q = self.mlp(q, p + ".mlp.lin1", p + ".mlp.lin2", B * nq, D, 1024, D, "relu", resid=q)
-                q, qq = self.layernorm(q, p + ".norm3", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
-                k2 = self.mha(p + ".cross_attn_image_to_token", kk, qq, q, B, NT, nq, D // 2, resid=k)
-                k, kk = self.layernorm(k2, p + ".norm4", M, D, 1e-5, pe=kpe_tab, pe_rows=NT)
-                if l != 2:
-                    hs.append((q, k))
-            q = self.mha("neck.att.final_attn_token_to_image", qq, kk, k, B, nq, NT, D // 2, resid=q)
-            q = self.layernorm(q, "neck.att.norm_final_attn", B * nq, D, 1e-5)
-            hs.append((q, k))
+                    q = self.layernorm(q, p + ".norm2", B * nq, D, 1e-5)
+                    q = self.mlp(q, p + ".mlp.lin1", p + ".mlp.lin2", B * nq, D, 1024, D, "relu", resid=q)
+                    q, qq = self.layernorm(q, p + ".norm3", B * nq, D, 1e-5, pe=q0.t, pe_rows=B * nq, pe_var=q0)
+                    Ki, Vi = group(lambda: (proj(i2t, "k", qq, B * nq, D // 2), proj(i2t, "v", q, B * nq, D // 2)))
+            if l == 3:
+                break
+            h_tok = self._xrec(T)
+            self._xwait(h_tok, None)
+            k2 = self._attend(B, i2t, Qi, Ki, Vi, NT, nq, D // 2, k)
+            k, kk = self.layernorm(k2, p + ".norm4", M, D, 1e-5, pe=kpe_tab, pe_rows=NT)
+            if l != 2:
+                hs.append((q, k))
+        hs.append((q, k))
+
+        def lanes_begin():
+            self._in_lanes = True
+        h_join = self._xrec(T)
+        self._xwait(h_join, None, on_bwd=lanes_begin)
+        return q0, hs
+
+    def _gates(self, cx, xr, q0, hs):
+        """q_out = q0 + the three layers' queries, and the gated maps (is_vpu_model.py:106-121): x_i = x (1 + cg_i + sg_i) for
+        the (queries, keys) pairs ``hs``.  Returns (q_out, maps), maps = [xr, gated 0..2]."""
+        B, NT, M, nq, D = cx.B, cx.NT, cx.M, cx.nq, self.D
         q_out = Var(self._new(B * nq, D))
-        ops.add4(q0.t, hs[0][0].t, hs[1][0].t, hs[2][0].t, q_out.t, nQ)
-        if training:
+        ops.add4(q0.t, hs[0][0].t, hs[1][0].t, hs[2][0].t, q_out.t, B * nq * D)
+        if cx.training:
             def bwd_qout():       # the gradient of the sum goes to its four terms: one launch (vpu_fanout_add)
                 if q_out.g is None:
                     return
                 vs = (q0, hs[0][0], hs[1][0], hs[2][0])
-                if not self.r5_fused:
-                    for v in vs:
-                        self.acc(v, q_out.g)
-                    return
                 had = [v.g is not None for v in vs]
                 for v, h_ in zip(vs, had):
                     if h_:
@@ -1277,43 +1267,14 @@ class Engine:
                         v.g = torch.empty_like(q_out.g)
                 ops.fanout_add(q_out.g, [v.g for v in vs], had, q_out.g.numel())
             self.tape.append(bwd_qout)
-        # gates (is_vpu_model.py:106-121): x_i = x (1 + cg_i + sg_i) for the three (queries, keys) pairs -- round 5: the three
-        # gates in ONE statistics launch and ONE pass over x forward (vpu_gate_fwd_n), one row pass + one column launch backward
-        # (vpu_gate_bwd_n: dx summed in fp32 over the three gates, rounded once) instead of nine / six launches
-        maps = [xr]
-        ng = len(hs) if self.r5_fused else 0
-        for qi, ki in (() if self.r5_fused else hs):       # (``r5_fused`` = False: one gate at a time, three launches each way)
-            cg, sg = self._new(B, D, dtype=torch.float32), self._new(B, NT, dtype=torch.float32)
-            aq, ac = self._new(B, D, dtype=torch.int32), self._new(B, NT, dtype=torch.int32)
-            ops.gate_stats(qi.t, ki.t, cg, aq, sg, ac, B, nq, NT, D)
-            xg = Var(self._new(M, D))
-            ops.gate_apply(xr.t, cg, sg, xg.t, B, NT, D)
-            if training:
-                def bwd_gate(xg=xg, qi=qi, ki=ki, cg=cg, sg=sg, aq=aq, ac=ac):
-                    if xg.g is None:
-                        return
-                    if any(v.g is None for v in (qi, ki)):
-                        pend = [v for pair in hs for v in pair if v.g is None]
-                        pool = ops.zero_(torch.empty(sum(v.t.numel() for v in pend), device=self.dev, dtype=self.td))
-                        o_ = 0
-                        for v in pend:
-                            v.g = pool[o_:o_ + v.t.numel()].view_as(v.t)
-                            o_ += v.t.numel()
-                    accum = xr.g is not None
-                    if not accum:
-                        xr.g = torch.empty_like(xr.t)
-                    for t_ in (xr.g, qi.g, ki.g):
-                        self._writable(t_)
-                    part = self._new(B, 64, D, dtype=torch.float32)
-                    ops.gate_bwd(xg.g, xr.t, cg, aq, sg, ac, xr.g, accum, qi.g, ki.g, part, B, nq, NT, D)
-                self.tape.append(bwd_gate)
-            maps.append(xg)
+        # round 5: the three gates in ONE statistics launch and ONE pass over x forward (vpu_gate_fwd_n), one row pass + one
+        # column launch backward (vpu_gate_bwd_n: dx summed in fp32 over the three gates, rounded once)
+        ng = len(hs)
         cg, sg = self._new(ng, B, D, dtype=torch.float32), self._new(ng, B, NT, dtype=torch.float32)
         aq, ac = self._new(ng, B, D, dtype=torch.int32), self._new(ng, B, NT, dtype=torch.int32)
         xgs = [Var(self._new(M, D)) for _ in range(ng)]
-        if ng:
-            ops.gate_fwd_n([qi.t for qi, _ in hs], [ki.t for _, ki in hs], xr.t, [v.t for v in xgs], cg, aq, sg, ac, B, nq, NT, D)
-        if training and ng:
+        ops.gate_fwd_n([qi.t for qi, _ in hs], [ki.t for _, ki in hs], xr.t, [v.t for v in xgs], cg, aq, sg, ac, B, nq, NT, D)
+        if cx.training:
             def bwd_gates():
                 live = [i for i in range(ng) if xgs[i].g is not None]
                 if not live:
@@ -1341,11 +1302,13 @@ class Engine:
                                      NT, D)
                         accum = True
             self.tape.append(bwd_gates)
-        maps += xgs
-        if taps is not None:
-            taps["q_out"] = q_out.t
-        # FPN branches (is_vpu_model.py:55-86), channels-last
-        o = self.out_dims
+        if cx.taps is not None:
+            cx.taps["q_out"] = q_out.t
+        return q_out, [xr] + xgs
+
+    def _fpn(self, cx, maps):
+        """FPN branches (is_vpu_model.py:55-86), channels-last; returns feats = [(map, side)] at strides 4, 8, 16, 32."""
+        B, g, NT, M, D, o = cx.B, cx.g, cx.NT, cx.M, self.D, self.out_dims
         c4 = max(o[0] * 2, D // 2)
         a = self.conv_t2(maps[0], "neck.down_4.0", B, g, g, D, c4, gn_next=True)
         a = self.groupnorm(a, "neck.down_4.1", B, 4 * NT, c4, True)
@@ -1367,20 +1330,27 @@ class Engine:
         a = self.linear(a, "neck.down_32.2.weight", "neck.down_32.2.bias", B * h32 * h32, o[3], c32)
         d32 = self.groupnorm(a, "neck.down_32.3", B, h32 * h32, o[3], True)
         feats = [(d4, 4 * g), (d8, 2 * g), (d16, g), (d32, h32)]
-        if taps is not None:
+        if cx.taps is not None:
             for i, (f, s) in enumerate(feats):
-                taps[f"fpn{i}"] = f.t
-        # ---- a12: head (swin_transformer.py:723-767)
-        Cc = self.C
-        Hs = 4 * g
+                cx.taps[f"fpn{i}"] = f.t
+        return feats
+
+    def _head(self, cx, feats, q_out, drop_mask, materialize_aux):
+        """a12/a13: head (swin_transformer.py:723-767) and the final align_corners=True upsamples; returns (inst, aux)."""
+        B, H, W_, nq, o, tape = cx.B, cx.H, cx.W, cx.nq, self.out_dims, self.tape
+        Cc, Hs = self.C, 4 * cx.g
         HW4 = Hs * Hs
         # fusion_conv over the concat of the four resized maps, by linearity: each level's column block of the fusion weight
         # is applied at that level's own resolution, the low-resolution products are resized and summed into the
         # full-resolution one (vpu_upsum_relu) -- no [B*112^2, 1024] concat, a third of the fusion FLOPs
         wf, ldf = self.W("head.fusion_conv.conv.weight"), 4 * Cc
         gf = self.G("head.fusion_conv.conv.weight")
+        # The ReLU' hand-shake of backward, three parties, all in this method.  bwd_head runs first and sets ``relu_done`` when
+        # conv_seg's backward (the last writer of fused.g) has already applied fused's ReLU'; bwd_fusion reads it to skip its
+        # own mask pass, and sets ``ymask[i]`` when its dgrads apply the ReLU' of ys[i] in their epilogue; the backward of
+        # head.convs.i (Engine.linear, ``pre_masked`` = ymask[i]) reads that to skip its mask pass in turn.
+        relu_done, ymask = [False], [[False] for _ in range(4)]
         ys, zs = [], []
-        ymask = [[False] for _ in range(4)]     # set by bwd_fusion: its dgrads apply the ReLU' of ys[i] in their epilogue
         for i in range(4):
             f, s = feats[i]
             ys.append(self.linear(f, f"head.convs.{i}.conv.weight", f"head.convs.{i}.conv.bias", B * s * s, Cc, o[i],
@@ -1394,8 +1364,7 @@ class Engine:
             ops.gemm(ys[i].t, (wf[0], wf[1] + i * Cc), z, B * s * s, Cc, Cc, Cc, ldf, Cc, self.dt)
             zs.append((z, s, s))
         ops.upsum_relu(fused.t, zs, B, Hs, Hs, Cc, self.dt)
-        relu_done = [False]     # conv_seg's backward (the last writer of fused.g) has already applied fused's ReLU'
-        if training:
+        if cx.training:
             def bwd_fusion():
                 if fused.g is None:
                     return
@@ -1421,7 +1390,7 @@ class Engine:
         seg = self._new(B * HW4, dtype=torch.float32)
         ops.convseg_fwd(fused.t, self.Pm("head.conv_seg.weight"), self.Pm("head.conv_seg.bias"), drop_mask, seg,
                         B * HW4, HW4, Cc)
-        dm = c["head_d_model"]
+        dm = self.cfg["head_d_model"]
         query = self.mlp(q_out, "head.ffn_layer.lin1", "head.ffn_layer.lin2", B * nq, dm, 2 * dm, Cc, "relu")
         qn, fn = Var(torch.empty_like(query.t)), Var(torch.empty_like(fused.t))
         inv_q, inv_f = self._new(B * nq, dtype=torch.float32), self._new(B * HW4, dtype=torch.float32)
@@ -1430,11 +1399,10 @@ class Engine:
         sim = self._new(B, nq, HW4, dtype=torch.float32)
         ops.gemm(qn.t, fn.t, sim, nq, HW4, Cc, Cc, Cc, HW4, self.dt, flags=EPI_OUT_F32 | EPI_AFFINE, post_mul=0.5,
                  post_add=0.5, batch=B, inner=1, sA=(nq * Cc, 0), sB=(HW4 * Cc, 0), sC=(nq * HW4, 0))
-        if taps is not None:
-            taps["seg_lowres"] = seg.view(B, 1, Hs, Hs)
-            taps["sim_lowres"] = sim.view(B, nq, Hs, Hs)
-            taps["fused"] = fused.t
-        # ---- a13: final align_corners=True upsample
+        if cx.taps is not None:
+            cx.taps["seg_lowres"] = seg.view(B, 1, Hs, Hs)
+            cx.taps["sim_lowres"] = sim.view(B, nq, Hs, Hs)
+            cx.taps["fused"] = fused.t
         inst = self._new(B, 1, H, W_, dtype=torch.float32)
         ops.upsample_ac_fwd(seg, inst, B, Hs, Hs, H, W_)
         aux = None
@@ -1443,7 +1411,7 @@ class Engine:
             aux = self._new(B, nq, H, W_, dtype=torch.float32)
             ops.upsample_ac_fwd(sim, aux, B * nq, Hs, Hs, H, W_)
         tape.sim_low = self.sim_low
-        if training:
+        if cx.training:
             def bwd_head():
                 d_inst, d_aux, d_sim_low = tape.out_grads
                 if d_aux is not None or d_sim_low is not None:
@@ -1479,23 +1447,21 @@ class Engine:
                         fused.g = torch.empty_like(fused.t)
                         ops.head_grad_fused(fn.g, fn.t, inv_f, dseg, fused.t, self.Pm("head.conv_seg.weight"), drop_mask,
                                             fused.g, part, part_b, B * HW4, HW4, Cc)
-                        relu_done[0] = True
-                        # (conv_seg's weight / bias partial rows join the batched column sums of the norm layers: flush_colsums)
-                        self._convseg_sums(part, part_b, nb, Cc)
-                        return
-                    accum = fused.g is not None
-                    if not accum:
-                        fused.g = torch.empty_like(fused.t)
-                    self._writable(fused.g)
-                    # accum bit 1: fused.g is complete with this call -> it leaves multiplied by [fused > 0] (one pass less
-                    # over the 77-MB map than a separate ReLU' kernel)
-                    ops.convseg_bwd(dseg, fused.t, self.Pm("head.conv_seg.weight"), drop_mask, fused.g, int(accum) | 2, part,
-                                    part_b, B * HW4, HW4, Cc)
+                    else:
+                        accum = fused.g is not None
+                        if not accum:
+                            fused.g = torch.empty_like(fused.t)
+                        self._writable(fused.g)
+                        # accum bit 1: fused.g is complete with this call -> it leaves multiplied by [fused > 0] (one pass
+                        # less over the 77-MB map than a separate ReLU' kernel)
+                        ops.convseg_bwd(dseg, fused.t, self.Pm("head.conv_seg.weight"), drop_mask, fused.g, int(accum) | 2, part,
+                                        part_b, B * HW4, HW4, Cc)
                     relu_done[0] = True
-                    self._convseg_sums(part, part_b, nb, Cc)
-            # must run BEFORE the closures of query / fused: insert at the position just after they were recorded
+                    # conv_seg's weight / bias partial rows join the batched column sums of the norm layers (flush_colsums)
+                    self._csq.append((part, self.G("head.conv_seg.weight"), nb, Cc))
+                    self._csq.append((part_b, self.G("head.conv_seg.bias"), nb, 1))
+            # appended last = backward runs it first, before the closures of query / fused recorded above
             self.tape.append(bwd_head)
-        self.last_tape = tape if training else None
         return inst, aux
 
     def _mark_ready(self, first_name, next_name):

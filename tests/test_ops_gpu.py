@@ -2011,9 +2011,11 @@ def test_dropout_mask_and_fill(ops):
     for _ in range(2):
         g.replay(); torch.cuda.synchronize(); out.append(captured.clone())
     assert not torch.equal(out[0], out[1])
+    held = dict(O._drop_state)      # the captured launch reads THIS state tensor: it stays allocated and comes back below
     O._drop_state.clear()
     b = [O.dropout_mask(12, 256, 0.9, "cuda", seed=77) for _ in range(3)]
     assert all(torch.equal(x, y) for x, y in zip(a, b))
+    O._drop_state.update(held)
     # (seed, call number) live in device memory: a launch captured in a graph follows a re-seeding, and the pair can be
     # saved and restored (FusedAdam.state_dict carries it)
     O.dropout_seed("cuda", 77)
