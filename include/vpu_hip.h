@@ -273,7 +273,10 @@ int vpu_act_bwd(const void* dy, int64_t ld_dy, const void* aux, int64_t ld_aux, 
 /* PuE Gaussian vectors: _guassinvector_click/_box (is_vpu_model.py:189-291) + GaussianVector(_box)
  * (ops.py:39-202).  points fp32 [B][2n][3] (row,col,order); boxes int32 [B][5] or NULL (click mode);
  * lut = the 19-tap clip (ops.py:51-61).  out dtype [B][2*num_max][ld] with ld >= 2*img+3, pad columns zero.
- * out64 (optional, may be NULL) receives the float64 rows exactly as the reference returns them. */
+ * out64 (optional, may be NULL) receives the float64 rows exactly as the reference returns them.
+ * Extension (not in the reference): boxes[b][4] < 0, by convention the row (0, 0, 0, 0, -1), means "sample b carries no
+ * box": its rows are those of click mode, so one call serves a batch that mixes click and box samples.  An all-zero row
+ * keeps its reference meaning (it replaces slot 0 with an empty vector). */
 int vpu_pue_encode(const float* points, const int32_t* boxes, const float* lut, void* out, double* out64,
                    int32_t B, int32_t n, int32_t num_max, int32_t img, int32_t ld, int32_t dtype, void* stream);
 /* Scribble prompts (prompt type 2).  vpu_pue_scribble_rows: after vpu_pue_encode (click mode), the LAST valid positive row
@@ -387,7 +390,9 @@ int vpu_cc_table(const int32_t* roots, int32_t* slots, int32_t* table, int32_t k
 
 /* DistMaps disks (ops.py:347-379, use_disks, spatial_scale 1) + optional draw_box outline (is_model.py:97-121:
  * cv2.rectangle((x0, y0), (x1, y1), 255, 3) = the closed 4-segment poly-line through the same restated ThickLine as
- * vpu_draw_polyline, into channel 0 (slot < n) or 1).  out fp32 [B][2][H][W] in {0,1}. */
+ * vpu_draw_polyline, into channel 0 (slot < n) or 1).  out fp32 [B][2][H][W] in {0,1}.
+ * Extension, as in vpu_pue_encode: a sample with boxes[b][4] < 0 gets no outline (its planes are those of boxes == NULL);
+ * an all-zero row still draws the degenerate rectangle at the origin into channel 0, as the reference does. */
 int vpu_disk_maps(const float* points, const int32_t* boxes, float* out, int32_t B, int32_t n, int32_t H, int32_t W,
                   float radius, void* stream);
 

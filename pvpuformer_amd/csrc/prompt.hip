@@ -32,6 +32,8 @@ __global__ __launch_bounds__(256) void pue_encode_kernel(const float* __restrict
             x = (int)p[0];  // astype(int32): truncation toward zero (ops.py:81)
             y = (int)p[1];
         }
+        // (a row whose slot is negative -- the "no box in this row" mark (0, 0, 0, 0, -1) of a mixed click / box batch --
+        // matches no i >= 0: that sample is encoded exactly as with boxes == nullptr)
         if (boxes && boxes[b * 5 + 4] == i) {  // is_vpu_model.py:276-277: the box row replaces whatever was there
             const int* bx = boxes + b * 5;
             kind = 2;
@@ -392,11 +394,13 @@ __global__ __launch_bounds__(256) void draw_polyline_kernel(const int* __restric
 }
 
 // cv2.rectangle((x0, y0), (x1, y1), 255, 3) = the closed poly-line (x0,y0) (x1,y0) (x1,y1) (x0,y1): segment s runs from corner
-// s - 1 to corner s with an end cap at corner s (is_model.py:97-121; python floor division for the half sizes)
+// s - 1 to corner s with an end cap at corner s (is_model.py:97-121; python floor division for the half sizes).
+// A negative slot marks a sample without a box: nothing is drawn for it (block-uniform, before any barrier).
 __global__ __launch_bounds__(256) void draw_box_kernel(const int* __restrict__ boxes, float* __restrict__ disks, int n, int H, int W) {
     __shared__ TlSeg sg;
     const int seg = blockIdx.x, b = blockIdx.y;
     const int* bx = boxes + b * 5;
+    if (bx[4] < 0) return;
     const int ch = bx[4] < n ? 0 : 1;
     const int hw = fdiv(bx[2], 2), hh = fdiv(bx[3], 2);
     const int x0 = bx[0] - hw, x1 = bx[0] + hw, y0 = bx[1] - hh, y1 = bx[1] + hh;

@@ -978,6 +978,8 @@ class Engine:
                 materialize_aux=True, scribble=None, coord_override=None, prenorm=False):
         """image4 fp32 [B,4,H,W]; points fp32 [B,2n,3]; boxes int32 [B,5] (prompt_type 1); scribble (prompt_type 2) =
         (curve int32 [B,P,2] poly-line vertices, profiles float64 [B, 2*img] from isegm/model/scribble.py).
+        A box row with a negative slot, (0, 0, 0, 0, -1), marks a sample without a box: it is computed exactly as under
+        prompt_type 0 (no outline, no PuE row replaced), so one forward can mix click and box samples.
         Returns instances fp32 [B,1,H,W] (logits) and instances_aux fp32 [B,S,H,W].  ``materialize_aux=False`` skips the
         38.5 MB/img upsample of the P2CL similarities: aux is None, the low-resolution planes stay in ``self.sim_low``
         [B,S,h,w] for the fused loss (ops.p2cl_up_fwd_bwd) and backward() takes their gradient as ``d_sim_low``.

@@ -295,25 +295,29 @@ class PromptState:
 
 
 def get_next_promts(pred, gt, points, state=None, pred_thresh=0.49, as_allmask=False, jitter_box=True,
-                    np_rng=np.random, rng=random):
+                    np_rng=np.random, rng=random, with_scribbles=False):
     """trainer.py:703-768.  pred [B,1,H,W] probabilities, gt [B,1,H,W], points [B,2n,3] (tensors).  Returns
     (points, boxes int32 [B,5]) as tensors on points' device and updates ``state`` (the slot that received the click now
-    predicts the false-negative / false-positive mask of this round)."""
+    predicts the false-negative / false-positive mask of this round).  ``with_scribbles``: also ``cal_scribble(gt > 0.5)``
+    as a third value, drawn where the reference draws it (trainer.py:725): after the box, before the next click."""
     dev = points.device
     if pred.is_cuda:
-        return _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitter_box, np_rng, rng)
+        return _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitter_box, np_rng, rng, with_scribbles)
     pred_np = pred.detach().float().cpu().numpy()[:, 0]
     gt_np = gt.detach().cpu().numpy()[:, 0] > 0.5
     pts_np = points.detach().float().cpu().numpy()
     fn0 = np.logical_and(gt_np, pred_np < pred_thresh)
     fp0 = np.logical_and(np.logical_not(gt_np), pred_np > pred_thresh)
     boxes = cal_box(gt_np, fn0, fp0, pts_np, as_allmask=as_allmask, jitter_box=jitter_box, rng=rng)
+    scribbles = cal_scribble(gt_np, rng=rng, np_rng=np_rng) if with_scribbles else None
     new_pts, picks, fn, fp = next_click(pred_np, gt_np, pts_np, pred_thresh, np_rng,
                                         device=pred.device if pred.is_cuda else None)
     if state is not None:
         for b, pk in enumerate(picks):
             if pk is not None:
                 state.assign(b, pk[0], fn[b] if pk[1] else fp[b])
+    if with_scribbles:
+        return torch.from_numpy(new_pts).to(dev), torch.from_numpy(boxes).to(dev), scribbles
     return torch.from_numpy(new_pts).to(dev), torch.from_numpy(boxes).to(dev)
 
 
@@ -323,7 +327,7 @@ def get_iou(pred, gt, pred_thresh=0.49):
     return (pm & gm).sum() / (pm | gm).sum()
 
 
-def _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitter_box, np_rng, rng):
+def _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitter_box, np_rng, rng, with_scribbles=False):
     """get_next_promts with the masks, distance transforms, maxima and the k-th-candidate lookup on the GPU: what crosses
     to the host per call is one uint8 mask per sample (for the connected-component labelling of cal_box), a few scalars
     per sample and the chosen coordinates -- not 2B float distance maps.  Same random draws in the same order, same
@@ -383,6 +387,7 @@ def _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitte
         xc, yc, bw, bh = int(0.5 * (x0 + x1)), int(0.5 * (y0 + y1)), int(x1 - x0), int(y1 - y0)
         if xc >= 1 and yc >= 1 and bw >= 1 and bh >= 1:
             boxes[b] = (xc, yc, bw, bh, loc)
+    scribbles = cal_scribble(g.cpu().numpy(), rng=rng, np_rng=np_rng) if with_scribbles else None     # trainer.py:725
     # ---- next_click (trainer.py:615-654, 733-764)
     dts = ops.chamfer5(torch.cat([fn, fp], 0).to(torch.uint8), zero_border=True)           # [2B, H, W] (cv2 DIST_L2, 5)
     mx = dts.flatten(1).amax(1).cpu().numpy()                                              # fn maxima, then fp maxima
@@ -409,6 +414,8 @@ def _get_next_promts_gpu(pred, gt, points, state, pred_thresh, as_allmask, jitte
         new_pts[b, loc] = (float(pos[b] // W), float(pos[b] % W), float(order))
         if state is not None:
             state.assign_device(b, loc, (fn if is_pos[b] else fp)[b])
+    if with_scribbles:
+        return torch.from_numpy(new_pts).to(dev), torch.from_numpy(boxes).to(dev), scribbles
     return torch.from_numpy(new_pts).to(dev), torch.from_numpy(boxes).to(dev)
 
 

@@ -38,7 +38,16 @@ More components in a group than the kernel's table holds (salt-and-pepper masks;
 back with the read-back; the forward of that group is discarded and its objects repeat the click with boxes from the host
 code (``_host_boxes``: ``crop_resize`` + ``prompt_sim.cal_box``, also ``_HostOps``' stand-in).  The sequential path also
 runs ``prompt_sim.next_click`` on every box-prompt click and so advances the global numpy generator for a click it
-discards; the batched path does not.  No result depends on it (the evaluation clicks come from the Clicker)."""
+discards; the batched path does not.  No result depends on it (the evaluation clicks come from the Clicker).
+
+Prompt schedules (``as_prompt_type`` a sequence or a callable, ``vpu_evaluation.PromptSchedule``).  Every object carries
+the type of its current click (asked once, when the click is made; a repeated click keeps it).  With a constant type the
+groups are the ones above.  With a schedule the objects of a step that share a network input size go through ONE forward,
+whatever their types: the box rows are still derived in sub-batches keyed by (mask size, host fallback) and scattered on the
+device into an ``int32 [rows, 5]`` tensor pre-filled with (0, 0, 0, 0, -1); a negative slot tells the model that the row
+carries no box, and it computes that row exactly as under ``as_prompt_type=0`` (``is_vpu_model.forward``).  The forward is
+``as_prompt_type=1`` when at least one row has a box and a plain type-0 call when none has.  An overflow flag repeats the
+click of the objects of its sub-batch only; the other rows of the same forward keep their results."""
 import ctypes as C
 import struct
 
@@ -57,10 +66,13 @@ _FLAGS_PER_ROW = 12        # int32 flags in one 48-byte row appended to the read
 def batchable(predictor, callback=None, as_prompt_type=0):
     """True when ``evaluate_dataset`` may run ``predictor`` batched: a ``BasePredictor`` whose transforms are only
     [ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip] (in that order, each optional), no
-    callback and click or box prompts (``as_prompt_type`` 0 or 1; ``get_vqu_prediction`` passes no scribbles, so type 2
-    stays sequential)."""
+    callback and click or box prompts: ``as_prompt_type`` 0 or 1, a sequence of those, or a callable (scribbles are not
+    batched, so type 2 and every sequence that holds a 2 stay sequential; a callable is only known to return 2 when it
+    does: ``BatchedEvaluator`` raises then)."""
     from .predictors.base import BasePredictor
-    if not isinstance(predictor, BasePredictor) or callback is not None or as_prompt_type not in (0, 1):
+    from .vpu_evaluation import prompt_schedule
+    values = prompt_schedule(as_prompt_type).values
+    if not isinstance(predictor, BasePredictor) or callback is not None or (values is not None and 2 in values):
         return False
     ts, i = list(predictor.transforms), 0
     if i < len(ts) and type(ts[i]) is ZoomIn:
@@ -145,6 +157,8 @@ class _Object:
         self.clear_at = -1             # pixel of the click made this step (cleared in the not-clicked map)
         self.recalc = False            # re-run the current click (ZoomIn.check_possible_recalculation fired)
         self.host_box = False          # re-run the current click with boxes from the host (component table overflow)
+        self.ptype = 0                 # prompt type of the current click (asked of the schedule when the click is made)
+        self.box_key = None            # (mask size, host fallback) of its box row in the current step; None: no box
         self.done = False
         self.plan = None
 
@@ -313,7 +327,8 @@ class BatchedEvaluator:
     def __init__(self, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20, as_prompt_type=0):
         assert batchable(predictor, None, as_prompt_type), \
             "the predictor's transforms or the prompt type are not the batched path's (see batchable)"
-        self.pred, self.K, self.prompt_type = predictor, int(batch_objects), int(as_prompt_type)
+        from .vpu_evaluation import prompt_schedule
+        self.pred, self.K, self.schedule = predictor, int(batch_objects), prompt_schedule(as_prompt_type)
         self.max_iou_thr, self.pred_thr, self.min_clicks, self.max_clicks = max_iou_thr, pred_thr, min_clicks, max_clicks
         self.zoom = predictor.zoom_in
         self.flip = any(type(t) is AddHorizontalFlip for t in predictor.transforms)
@@ -421,6 +436,11 @@ class BatchedEvaluator:
                 at = fn_at if positive else fp_at
                 o.clicks.append(Click(is_positive=bool(positive), coords=at, indx=len(o.clicks)))
                 o.clear_at = at[0] * o.W + at[1]
+                o.ptype = self.schedule(len(o.clicks) - 1, o.ious[-1] if o.ious else 0)
+                if o.ptype == 2:
+                    raise ValueError("the prompt schedule returned 2 (scribble) inside the batched loop, which has no scribble "
+                                     "prompts: evaluate this schedule on the sequential path (evaluate_sample, or "
+                                     "evaluate_dataset with batch_objects=1)")
             o.plan = self._plan(o)
         # the refill queue: as many prepared objects (first keys known) as slots could free up
         new = []
@@ -432,27 +452,40 @@ class BatchedEvaluator:
         key_objs = stepping + [o for o in active if o.keys is None] + new
         ops = self.ops
         row = {id(o): i for i, o in enumerate(key_objs)}
-        # size groups, split by prompt type: a click that ZoomIn re-runs goes through get_prediction, i.e. as clicks only.
-        # The box masks have the network's size except when a held roi meets an un-zoomed step (no prediction to zoom on):
-        # the sequential path then still crops them to target_size, so that size is part of the key
+        # A click that ZoomIn re-runs goes through get_prediction, i.e. as clicks only (kind 0).  The box masks have the
+        # network's size except when a held roi meets an un-zoomed step (no prediction to zoom on): the sequential path then
+        # still crops them to target_size, so that size is part of a box sub-batch's key.  Constant type: one forward per
+        # (size, kind, box size, host fallback), as ever.  Schedule: one forward per size, its box rows in sub-batches
+        mixed = self.schedule.constant is None
         groups = {}
         for o in stepping:
-            kind = 0 if o.recalc else self.prompt_type
-            box_size = None
+            kind = 0 if o.recalc else o.ptype
+            box_key = None
             if kind == 1:
-                box_size = tuple(self.zoom.target_size) if o.roi is not None else (o.H, o.W)
-            groups.setdefault((o.plan[1], kind, box_size, o.host_box), []).append(o)
-        n_flags = sum(1 for key in groups if key[1] == 1)
+                box_key = (tuple(self.zoom.target_size) if o.roi is not None else (o.H, o.W), o.host_box)
+            o.box_key = box_key
+            groups.setdefault((o.plan[1],) if mixed else (o.plan[1], kind) + (box_key or (None, o.host_box)), []).append(o)
+        spans, n_flags = [], 0
+        for key, members in groups.items():
+            subs = {}
+            for j, o in enumerate(members):
+                if o.box_key is not None:
+                    subs.setdefault(o.box_key, []).append(j)
+            n_flags += len(subs)
+            spans.append([key[0], members, subs])
         ops.begin(len(key_objs), n_flags)
-        spans = []
-        for (size, kind, box_size, host_box), members in groups.items():
-            bfirst, brows = None, []
-            if kind == 1:
+        for span in spans:
+            size, members, subs = span
+            box_batches = []
+            for (box_size, host_box), js in subs.items():
+                bfirst, brows = None, []
                 for mirror in ((False, True) if self.flip else (False,)):
-                    for o in members:
+                    for j in js:
+                        o = members[j]
                         brows.append((o, o.roi, mirror, self._own_rows(o.clicks)))
                         i = ops.add_box(*brows[-1])
                         bfirst = i if bfirst is None else bfirst
+                box_batches.append((box_size, host_box, js, bfirst, brows))
             first = None
             for j, o in enumerate(members):
                 i = ops.add(o, o.plan[0], j, row[id(o)], prev=self.prev_channel)
@@ -461,28 +494,41 @@ class BatchedEvaluator:
             for j, o in enumerate(members):
                 i = ops.add(o, o.plan[3], j, row[id(o)])
                 pfirst = i if pfirst is None else pfirst
-            spans.append((size, members, first, pfirst, kind, box_size, host_box, bfirst, brows))
+            span[2:] = [first, pfirst, box_batches]
         kfirst = None
         for o in key_objs:
             i = ops.add(o, Roi.whole(o.H, o.W), 0, row[id(o)])
             kfirst = i if kfirst is None else kfirst
         ops.upload()
         flag_of, n_box = {}, 0
-        for size, members, first, pfirst, kind, box_size, host_box, bfirst, brows in spans:
+        for size, members, first, pfirst, box_batches in spans:
             image_nd = ops.resize(members, first, len(members), size, self.flip, 4 if self.prev_channel else 3)
             lists = [o.plan[2] for o in members]
             if self.flip:
                 lists = lists + [[c.copy(coords=(c.coords[0], size[1] - c.coords[1] - 1)) for c in cl] for cl in lists]
             points_nd = self.pred.get_points_nd(lists).float()
-            boxes = None
-            if kind == 1:
+            boxes, kind = None, 0
+            for box_size, host_box, js, bfirst, brows in box_batches:
                 n_batch, target = points_nd.shape[1] // 2, (self.zoom.target_size if self.zoom else None)
+                whole = len(js) == len(members)
+                at = None            # rows of this sub-batch in the forward: its objects, then their flip copies
+                if not whole:
+                    at = torch.tensor(js + ([len(members) + j for j in js] if self.flip else []), device=self.device)
+                pts = points_nd if whole else points_nd[at]
                 if host_box:
-                    boxes = torch.from_numpy(_host_boxes(brows, points_nd, n_batch, box_size, target)).to(self.device)
+                    got = torch.from_numpy(_host_boxes(brows, pts, n_batch, box_size, target)).to(self.device)
                 else:
-                    boxes = ops.boxes(brows, bfirst, points_nd, n_batch, box_size, target, n_box)
-                    flag_of.update((id(o), n_box) for o in members)
+                    got = ops.boxes(brows, bfirst, pts, n_batch, box_size, target, n_box)
+                    flag_of.update((id(members[j]), n_box) for j in js)
                 n_box += 1
+                if whole:
+                    boxes = got
+                else:
+                    if boxes is None:        # a row without a box: slot -1 (is_vpu_model.forward)
+                        boxes = torch.zeros(points_nd.shape[0], 5, dtype=torch.int32, device=self.device)
+                        boxes[:, 4] = -1
+                    boxes[at] = got.to(self.device)
+                kind = 1
             logits = self.pred.net(image_nd, points_nd, (points_nd, boxes, None), kind)['instances']
             if tuple(logits.shape[2:]) != tuple(image_nd.shape[2:]):
                 from .transforms import resize_align_corners

@@ -12,14 +12,16 @@ from ..transforms import AddHorizontalFlip, LimitLongestSide, SigmoidForPred, cr
 class BasePredictor:
     def __init__(self, model, device, net_clicks_limit=None, with_flip=False, with_sigmoid=True, zoom_in=None,
                  max_size=None, cascade_step=0, cascade_adaptive=False, cascade_clicks=1, **kwargs):
-        # base.py:109-125 -- the cascade re-prediction of the first clicks and the per-click model list (`model` given as a
-        # (net, click_models) tuple) are side branches the shipped evaluation never takes (scripts/evaluate_vpumodel.py:187-192
-        # passes neither): not mirrored, and refused here rather than silently ignored
-        if cascade_step:
-            raise NotImplementedError("BasePredictor(cascade_step > 0): the cascade branch of base.py:109-119 is not mirrored")
+        # base.py:109-125 -- the cascade re-prediction of the first clicks (cascade_step >= 2) and the per-click model list
+        # (`model` given as a (net, click_models) tuple) are side branches that are not mirrored, and refused here rather than
+        # silently ignored.  cascade_step = 1 is what the shipped script passes with its default
+        # --cf-n 0 (scripts/evaluate_vpumodel.py:160-165: cascade_step = cf_n + 1): one inner call and return, i.e. the plain
+        # path, except that the caller's ``prev_mask`` is dropped during the first ``cascade_clicks`` clicks (base.py:111, :64)
+        if cascade_step and int(cascade_step) != 1:
+            raise NotImplementedError("BasePredictor(cascade_step >= 2): the cascade branch of base.py:109-119 is not mirrored")
         if isinstance(model, tuple):
             raise NotImplementedError("BasePredictor(model=(net, click_models)): the per-click model list of base.py:121-125 is not mirrored")
-        self.cascade_step, self.cascade_adaptive, self.cascade_clicks = 0, bool(cascade_adaptive), cascade_clicks
+        self.cascade_step, self.cascade_adaptive, self.cascade_clicks = int(cascade_step or 0), bool(cascade_adaptive), cascade_clicks
         self.click_models, self.model_indx = None, 0
         self.net, self.device = model, device
         self.net_clicks_limit, self.with_flip, self.with_sigmoid = net_clicks_limit, with_flip, with_sigmoid
@@ -72,6 +74,8 @@ class BasePredictor:
 
     def _net_input(self, clicker, prev_mask):
         clicks_list = clicker.get_clicks()
+        if self.cascade_step and len(clicks_list) <= self.cascade_clicks:
+            prev_mask = None            # base.py:62-64, 109-111: the single cascade pass runs on the predictor's own mask
         prev_mask = self.prev_prediction if prev_mask is None else prev_mask
         image_nd = torch.cat((self.original_image, prev_mask), dim=1) if self.net.with_prev_mask else self.original_image
         image_nd, clicks_lists, _ = self.apply_transforms(image_nd, [clicks_list])
@@ -99,13 +103,14 @@ class BasePredictor:
     def get_vqu_prediction(self, clicker, prev_mask=None, on_cascade=False, gt_mask=None, as_prompt_type=0,
                            click_indx=0, as_multi_prompts=True):
         """base.py:106-151,166-177: the model also receives the box prompt derived from (prev_mask, gt), both cropped to
-        the ZoomIn region of interest."""
+        the ZoomIn region of interest, and with ``as_prompt_type=2`` the scribble simulated on the same ground truth rows
+        (trainer.py:725; ``prompts[2]`` stays None for the other types, whose network never reads it)."""
         if not as_multi_prompts:
             raise NotImplementedError("get_vqu_prediction(as_multi_prompts=False): the get_next_promts_inference branch of "
                                       "base.py:154-164 is not mirrored (the shipped evaluation passes True, vpu_evaluation.py:43)")
         image_nd, clicks_lists, prev = self._net_input(clicker, prev_mask)
         points_nd = self.get_points_nd(clicks_lists).float()
-        boxes = None
+        boxes = scribbles = None
         if as_prompt_type != 0 or self.always_simulate_prompts:
             # the reference derives the box prompt on EVERY click (base.py:176), also for click prompts, where the network
             # never reads it: here it is simulated only when it is consumed (~3 ms of a 7.5-ms click otherwise) -- by the
@@ -118,8 +123,12 @@ class BasePredictor:
             if self.zoom_in is not None and self.zoom_in._object_roi is not None:
                 gt = crop_resize(gt, self.zoom_in._object_roi, self.zoom_in.target_size)
                 prev = crop_resize(prev, self.zoom_in._object_roi, self.zoom_in.target_size)
-            _, boxes = get_next_promts(prev, gt, points_nd, None, as_allmask=False, jitter_box=False)
-        prompts = (points_nd, boxes, None)
+            if as_prompt_type == 2:
+                _, boxes, scribbles = get_next_promts(prev, gt, points_nd, None, as_allmask=False, jitter_box=False,
+                                                      with_scribbles=True)
+            else:
+                _, boxes = get_next_promts(prev, gt, points_nd, None, as_allmask=False, jitter_box=False)
+        prompts = (points_nd, boxes, scribbles)
         logits = self.net(image_nd, points_nd, prompts, as_prompt_type)['instances']
         pred = self._finish(logits, image_nd)
         if self.zoom_in is not None and self.zoom_in.check_possible_recalculation():

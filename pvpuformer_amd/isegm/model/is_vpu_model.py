@@ -173,7 +173,12 @@ class VitMultiGaussianVector_ed_Model(ISModel):
         """image [B,4,H,W] (rgb in [0,1] + previous mask), points [B,2n,3] (row, col, order; -1 pad),
         prompts = (points, boxes[B,5] int32, scribbles) for as_prompt_type 1 and 2; scribbles = [points array [B,1,P,2] of
         (x, y), bounding rectangles [B,1,4] of (x_center, y_center, width, height)] as ``cal_scribble`` returns them
-        (numpy, not tensors: trainer.py:1192-1243) (is_vpu_model.py:383-438)."""
+        (numpy, not tensors: trainer.py:1192-1243) (is_vpu_model.py:383-438).
+
+        Extension (not in the reference): with ``as_prompt_type=1`` a row ``boxes[b] = (0, 0, 0, 0, -1)`` (any negative
+        slot) says that sample b carries no box; it is computed exactly as under ``as_prompt_type=0``.  ``cal_box`` never
+        produces a negative slot, and an all-zero row keeps its reference meaning (it replaces slot 0 and draws the
+        degenerate rectangle at the origin).  The batched evaluation uses it to run click and box rows in one forward."""
         eng = self._ensure_engine()
         points, boxes, scribble = self._unpack_prompts(points, prompts, as_prompt_type, edloss)
         image = image.contiguous().float()

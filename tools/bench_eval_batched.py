@@ -6,7 +6,9 @@ per second and milliseconds per click for each K, and the share of the time spen
 synchronised pass).  K = 1 is the sequential loop (evaluate_sample per object).  ``--prompt-type 1`` evaluates with box
 prompts (BasePredictor.get_vqu_prediction derives the box per click sequentially, vpu_box_prompts_batched per step batched)
 and also counts, with the torch profiler, the device-to-host copies of a batched step (expected: exactly one).
-usage: python tools/bench_eval_batched.py [--prompt-type {0,1}] [objects] [K ...]"""
+``--prompt-type 1,0`` is a per-click schedule (a box on the first click, then clicks; the last element repeats): the batched
+steps then run click and box rows in one forward, and ``forwards_per_step`` reports it.
+usage: python tools/bench_eval_batched.py [--prompt-type {0,1,LIST}] [objects] [K ...]"""
 import argparse
 import json
 import os
@@ -73,9 +75,18 @@ def d2h_copies_per_step(run):
     return sum(1 for n in names if "dtoh" in n.lower().replace(" ", "") or "device -> host" in n.lower()), len(steps)
 
 
+def prompt_type(text):
+    """"1" -> 1; "1,0" -> (1, 0).  Types 0 and 1 only: scribble prompts are not batched."""
+    types = tuple(int(v) for v in text.split(","))
+    if not types or any(t not in (0, 1) for t in types):
+        raise argparse.ArgumentTypeError("0, 1 or a comma list of them")
+    return types[0] if len(types) == 1 else types
+
+
 def main():
+    from pvpuformer_amd.isegm.inference import batched
     ap = argparse.ArgumentParser()
-    ap.add_argument("--prompt-type", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--prompt-type", type=prompt_type, default=0)
     ap.add_argument("objects", nargs="?", type=int, default=32)
     ap.add_argument("ks", nargs="*", type=int)
     args = ap.parse_args()
@@ -100,8 +111,12 @@ def main():
         secs = time.perf_counter() - t0
         clicks = sum(len(s) for s in series)
         # forward share: the same run with the forward synchronised on both sides
-        fwd = []
-        orig = model.forward
+        fwd, steps = [], []
+        orig, orig_step = model.forward, batched.BatchedEvaluator._step
+
+        def counted_step(self, *a, **k):
+            steps.append(1)
+            return orig_step(self, *a, **k)
 
         def timed(*a, **k):
             torch.cuda.synchronize(); t = time.perf_counter()
@@ -109,15 +124,19 @@ def main():
             torch.cuda.synchronize(); fwd.append(time.perf_counter() - t)
             return out
         model.forward = timed
+        batched.BatchedEvaluator._step = counted_step
         try:
             t1 = time.perf_counter()
             evaluate_dataset(ds, mk(), batch_objects=K, batch_box_prompts=True, **kw)
             secs_sync = time.perf_counter() - t1
         finally:
             model.forward = orig
+            batched.BatchedEvaluator._step = orig_step
         res[K] = dict(object_clicks_per_s=round(clicks / secs, 1), ms_per_click=round(secs / clicks * 1e3, 3),
                       ms_per_step=round(secs / len(fwd) * 1e3, 2),
                       forwards=len(fwd), forward_share=round(sum(fwd) / secs_sync, 3), object_clicks=clicks)
+        if len(steps) > 1:       # (the first step of a run only computes click keys: it has no forward)
+            res[K].update(steps=len(steps), forwards_per_step=round(len(fwd) / (len(steps) - 1), 3))
     k1 = res.get(1, {}).get("object_clicks_per_s")
     line = {"bench": "eval_batched", "model": "vitb448", "dtype": "bf16", "objects": n_obj, "max_clicks": 20, "prompt_type": ptype,
             "results": {str(k): v for k, v in res.items()}}
@@ -126,10 +145,10 @@ def main():
     if 1 in res and len(res) > 1:
         line["batched_over_sequential_ms_per_click"] = {str(k): round(v["ms_per_click"] / res[1]["ms_per_click"], 3)
                                                         for k, v in res.items() if k != 1}
-    if ptype == 1 and max(ks) > 1:
+    if ptype != 0 and max(ks) > 1:
         copies, steps = d2h_copies_per_step(
             lambda: evaluate_dataset(warm, mk(), batch_objects=max(ks), batch_box_prompts=True, max_iou_thr=2.0, max_clicks=4,
-                                     as_prompt_type=1))
+                                     as_prompt_type=ptype))
         line["batched_step_d2h_copies"] = {"K": max(ks), "steps": steps, "device_to_host_copies": copies}
     print(json.dumps(line))
 
