@@ -351,6 +351,25 @@ int vpu_roi_paste_batched(const vpu_eval_obj* objs, int32_t n, const float* prob
  * uint8, scratch int32 and dist fp32, each [2n][Hm][Wm], Hm >= every H, Wm >= every W, Wm % 4 == 0; max_hw >= every H * W. */
 int vpu_click_keys_batched(const vpu_eval_obj* objs, int32_t n, uint8_t* err, int32_t* scratch, float* dist, int32_t Hm,
                            int32_t Wm, int32_t max_hw, void* stream);
+/* Interactive sessions served through one batched forward (pvpuformer_amd/isegm/inference/sessions.py): what an annotation
+ * tool needs of a click, without ground truth.  One launch covers n sessions of different image sizes:
+ *   canvas fp32 [H][W] (16-byte aligned), bits = ceil(H * W / 64) little-endian 64-bit words (8-byte aligned), rec = int32 [8],
+ *   the inclusive roi (r0, r1, c0, c1) inside [H][W], src = the session's map in probs. */
+typedef struct vpu_session_obj {
+    float* canvas;
+    uint64_t* bits;
+    int32_t* rec;
+    int32_t H, W, r0, r1, c0, c1, src, reserved;
+} vpu_session_obj;
+/* canvas = what vpu_roi_paste_batched writes (probs fp32 [*][S_h][S_w], map src, resized to the roi's size and pasted into
+ * zeros; a roi of the map's size is copied).  bits: pixel i = r * W + c is bit i & 63 of word i >> 6, set when canvas >
+ * pred_thr (strict); bits at or beyond H * W are zero.  rec = {|canvas > pred_thr|, then vpu_mask_bbox's {count, rmin, rmax,
+ * cmin, cmax} of canvas > box_thr without clicks ({0, H, -1, W, -1} when empty), 0, 0}.  Every word is written by the one wave
+ * that owns it, with a plain store.  form 0: one pixel per lane, the word is the wave's ballot; form 1: four pixels per lane
+ * (16-byte canvas stores), the nibbles of 16 lanes joined by shuffles.  Both write the same bytes.  max_hw >= every H * W.
+ * Neither allocates nor synchronises. */
+int vpu_session_paste_batched(const vpu_session_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w,
+                              float pred_thr, float box_thr, int32_t max_hw, int32_t form, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

@@ -66,6 +66,13 @@ class BoxRow(C.Structure):
                 ("c1", C.c_int32), ("mirror", C.c_int32), ("n_obj", C.c_int32)]
 
 
+class SessionObj(C.Structure):
+    """vpu_session_obj (include/vpu_hip.h): one session of vpu_session_paste_batched."""
+    _fields_ = [("canvas", C.c_void_p), ("bits", C.c_void_p), ("rec", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("r0", C.c_int32), ("r1", C.c_int32), ("c0", C.c_int32),
+                ("c1", C.c_int32), ("src", C.c_int32), ("reserved", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -112,6 +119,7 @@ SIGNATURES = {
     "vpu_error_masks": [_P, _P, _P, _P, _I, _I, _P],
     "vpu_roi_resize_batched": [_P, _I, _P, _I, _I, _I, _I, _P],
     "vpu_roi_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _P],
+    "vpu_session_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_disk_maps": [_P, _P, _P, _I, _I, _I, _I, _F, _P],

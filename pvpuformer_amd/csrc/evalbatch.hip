@@ -349,7 +349,153 @@ __global__ __launch_bounds__(256) void box_finish_kernel(const vpu_box_row* __re
     for (int k = 0; k < 5; ++k) boxes[5 * row + k] = out[k];
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (5) interactive sessions (isegm/inference/sessions.py): the paste of (2) without ground truth, plus what the caller of
+//     a click wants back: the mask canvas > pred_thr at one bit per pixel, its area, and the ZoomIn box of canvas > box_thr.
+//     rec (int32 [8]): {area, count, rmin, rmax, cmin, cmax, 0, 0}, set by session_init_kernel.
+//     Pixel i is bit i & 63 of word i >> 6: 64 consecutive pixels make a word, and a wave has 64 lanes, so every word is
+//     produced inside one wave and written once with a plain store (no atomics on the packed buffer, no zero-fill first).
+struct SessionAcc {
+    int area = 0, cnt = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
+};
+
+// canvas value of pixel i: paste_pixel's expression, so the canvas has vpu_roi_paste_batched's bits
+__device__ __forceinline__ float session_pixel(const vpu_session_obj& d, const float* __restrict__ src, int S_h, int S_w, bool copy,
+                                               float sh, float sw, float box_thr, int64_t i, SessionAcc& a) {
+    const int r = (int)(i / d.W), c = (int)(i - (int64_t)r * d.W);
+    float v = 0.f;
+    if (r >= d.r0 && r <= d.r1 && c >= d.c0 && c <= d.c1)
+        v = copy ? src[(int64_t)(r - d.r0) * S_w + (c - d.c0)] : ac_sample(src, S_w, S_h, S_w, sh, sw, r - d.r0, c - d.c0);
+    if (v > box_thr) {
+        ++a.cnt;
+        a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
+    }
+    return v;
+}
+
+__global__ void session_init_kernel(const vpu_session_obj* __restrict__ objs, int n) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    const vpu_session_obj& d = objs[b];
+    int* s = d.rec;
+    s[0] = 0; s[1] = 0; s[2] = d.H; s[3] = -1; s[4] = d.W; s[5] = -1; s[6] = 0; s[7] = 0;
+}
+
+// block reduction as in roi_paste_kernel: wave shuffles, the four waves' partials through LDS, one atomic per block and counter
+__device__ __forceinline__ void session_reduce(const vpu_session_obj& d, SessionAcc a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.area += __shfl_xor(a.area, o, 64); a.cnt += __shfl_xor(a.cnt, o, 64);
+        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
+        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
+    }
+    __shared__ int red[4][6];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = a.area; red[wave][1] = a.cnt;
+        red[wave][2] = a.r0; red[wave][3] = a.r1; red[wave][4] = a.c0; red[wave][5] = a.c1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            red[0][0] += red[k][0]; red[0][1] += red[k][1];
+            red[0][2] = min(red[0][2], red[k][2]); red[0][3] = max(red[0][3], red[k][3]);
+            red[0][4] = min(red[0][4], red[k][4]); red[0][5] = max(red[0][5], red[k][5]);
+        }
+        int* s = d.rec;
+        if (red[0][0]) atomicAdd(s + 0, red[0][0]);
+        if (red[0][1]) {
+            atomicAdd(s + 1, red[0][1]);
+            atomicMin(s + 2, red[0][2]); atomicMax(s + 3, red[0][3]); atomicMin(s + 4, red[0][4]); atomicMax(s + 5, red[0][5]);
+        }
+    }
+}
+
+// form 0: one pixel per lane; a wave's ballot over its 64 consecutive pixels is the word.  The loop runs over words and its
+// bounds depend on the wave only, so all 64 lanes reach the ballot; lanes past H * W vote 0 (the padding bits)
+__global__ __launch_bounds__(256) void session_paste_ballot_kernel(const vpu_session_obj* __restrict__ objs,
+                                                                   const float* __restrict__ probs, int S_h, int S_w,
+                                                                   float pred_thr, float box_thr) {
+    const vpu_session_obj& d = objs[blockIdx.y];
+    const int h = d.r1 - d.r0 + 1, w = d.c1 - d.c0 + 1;
+    const bool copy = h == S_h && w == S_w;
+    const float sh = ac_scale(S_h, h), sw = ac_scale(S_w, w);
+    const float* src = probs + (int64_t)d.src * S_h * S_w;
+    const int64_t HW = (int64_t)d.H * d.W, words = (HW + 63) >> 6;
+    const int lane = threadIdx.x & 63;
+    SessionAcc a;
+    for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < words; k += (int64_t)gridDim.x * 4) {
+        const int64_t i = (k << 6) + lane;
+        bool m = false;
+        if (i < HW) {
+            const float v = session_pixel(d, src, S_h, S_w, copy, sh, sw, box_thr, i, a);
+            d.canvas[i] = v;
+            m = v > pred_thr;
+            a.area += m ? 1 : 0;
+        }
+        const unsigned long long word = __ballot(m);
+        if (lane == 0) d.bits[k] = word;
+    }
+    session_reduce(d, a);
+}
+
+// form 1: four pixels per lane (one 16-byte canvas store); a wave covers 256 pixels = 4 words per turn, lanes 16j..16j+15 hold
+// the nibbles of word j, joined by four xor-shuffles inside the 16-lane group; the group's first lane stores the word
+__global__ __launch_bounds__(256) void session_paste_quad_kernel(const vpu_session_obj* __restrict__ objs,
+                                                                 const float* __restrict__ probs, int S_h, int S_w,
+                                                                 float pred_thr, float box_thr) {
+    const vpu_session_obj& d = objs[blockIdx.y];
+    const int h = d.r1 - d.r0 + 1, w = d.c1 - d.c0 + 1;
+    const bool copy = h == S_h && w == S_w;
+    const float sh = ac_scale(S_h, h), sw = ac_scale(S_w, w);
+    const float* src = probs + (int64_t)d.src * S_h * S_w;
+    const int64_t HW = (int64_t)d.H * d.W, words = (HW + 63) >> 6, turns = (HW + 255) >> 8;
+    const int lane = threadIdx.x & 63;
+    SessionAcc a;
+    for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < turns; k += (int64_t)gridDim.x * 4) {
+        const int64_t i0 = (k << 8) + 4 * lane;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        unsigned nib = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i0 + u < HW) {
+                v[u] = session_pixel(d, src, S_h, S_w, copy, sh, sw, box_thr, i0 + u, a);
+                if (v[u] > pred_thr) { nib |= 1u << u; ++a.area; }
+            }
+        }
+        if (i0 + 3 < HW) {
+            *reinterpret_cast<float4*>(d.canvas + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {                                                  // the quad that holds the last H * W % 4 pixels
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u < HW) d.canvas[i0 + u] = v[u];
+        }
+        unsigned long long word = (unsigned long long)nib << (4 * (lane & 15));
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
+        const int64_t at = (k << 2) + (lane >> 4);
+        if ((lane & 15) == 0 && at < words) d.bits[at] = word;
+    }
+    session_reduce(d, a);
+}
+
 }  // namespace
+
+extern "C" int vpu_session_paste_batched(const vpu_session_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w,
+                                         float pred_thr, float box_thr, int32_t max_hw, int32_t form, void* stream) {
+    vpu_clear_stale_error();
+    if (!objs || !probs || n < 1 || n > 65535 || S_h < 1 || S_w < 1 || max_hw < 1 || (form != 0 && form != 1)) {
+        vpu_set_error("session_paste_batched: sizes (1 <= n <= 65535) or form (0: ballot, 1: quads)");
+        return VPU_ERR_ARG;
+    }
+    session_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    const int nb = vpu_grid_for(max_hw, 1024, 128);
+    if (form == 0)
+        session_paste_ballot_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, probs, S_h, S_w, pred_thr, box_thr);
+    else
+        session_paste_quad_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, probs, S_h, S_w, pred_thr, box_thr);
+    return vpu_check_launch("vpu_session_paste_batched");
+}
 
 extern "C" int vpu_box_prompts_batched(const vpu_box_row* rows, int32_t n_rows, const float* points, int32_t n_batch, int32_t S_h,
                                        int32_t S_w, float pred_thresh, uint8_t* masks, int32_t* counts, int32_t* roots,

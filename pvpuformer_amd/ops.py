@@ -446,6 +446,17 @@ def roi_paste_batched(objs, n, probs, S_h, S_w, pred_thr, box_thr, max_hw):
     _lib.call("vpu_roi_paste_batched", ptr(objs), n, ptr(probs), S_h, S_w, float(pred_thr), float(box_thr), max_hw, _stream())
 
 
+SESSION_PASTE_FORM = 1      # vpu_session_paste_batched: 0 = ballot, 1 = quads, the faster by DESIGN section 11's measurement
+
+
+def session_paste_batched(objs, n, probs, S_h, S_w, pred_thr, box_thr, max_hw, form=None):
+    """probs fp32 [*, S_h, S_w] pasted into the sessions' canvases (objs: device array of vpu_session_obj), with the packed
+    mask canvas > pred_thr, its area and the box of canvas > box_thr (vpu_session_paste_batched)."""
+    assert probs.dtype == torch.float32 and probs.is_contiguous()
+    _lib.call("vpu_session_paste_batched", ptr(objs), n, ptr(probs), S_h, S_w, float(pred_thr), float(box_thr), max_hw,
+              SESSION_PASTE_FORM if form is None else int(form), _stream())
+
+
 def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
     err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)

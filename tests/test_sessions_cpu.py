@@ -1,0 +1,217 @@
+"""CPU: ``SessionPool`` (isegm/inference/sessions.py) with a deterministic stub network and the host stand-ins of its two
+kernels, against one private ``BasePredictor`` per session fed the same click lists: probabilities and masks are equal
+after every call."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from pvpuformer_amd.isegm.inference import sessions
+from pvpuformer_amd.isegm.inference import transforms as T
+from pvpuformer_amd.isegm.inference.clicker import Click
+from pvpuformer_amd.isegm.inference.predictors import get_predictor
+from pvpuformer_amd.isegm.inference.sessions import SessionPool
+
+from sessions_cases import PRED_THR, StubNet, Twin, assert_equal, blob_image, step
+
+
+def _host_mask_box(prob, thr, positive_clicks=()):
+    m = (prob[0, 0] > thr).numpy().copy()
+    count = int(m.sum())
+    for r, c in positive_clicks:
+        m[int(r), int(c)] = True
+    rows, cols = np.nonzero(m)
+    if len(rows) == 0:
+        return 0, m.shape[0], -1, m.shape[1], -1
+    return count, int(rows.min()), int(rows.max()), int(cols.min()), int(cols.max())
+
+
+@pytest.fixture(autouse=True)
+def host_transforms(monkeypatch):
+    """The private predictors' ZoomIn on the host (its two device calls replaced by torch / numpy)."""
+    monkeypatch.setattr(T._device, "resize_align_corners",
+                        lambda x, size: F.interpolate(x.float(), size=tuple(int(s) for s in size), mode="bilinear",
+                                                      align_corners=True))
+    monkeypatch.setattr(T._device, "mask_box", _host_mask_box)
+
+
+def _predictor(skip_clicks=-1, **params):
+    return get_predictor(StubNet(), "NoBRS", "cpu", with_flip=True, predictor_params=params,
+                         zoom_in_params=dict(skip_clicks=skip_clicks, target_size=(32, 32), min_crop_size=12))
+
+
+SIZES = [(60, 80), (48, 48), (50, 70)]
+
+
+def _twins(pool, make, sizes=SIZES, radius=0.25):
+    out = []
+    for j, (H, W) in enumerate(sizes):
+        image, centre = blob_image(H, W, seed=j, radius=radius)
+        t = Twin(pool, make, image)
+        t.centre = centre
+        out.append(t)
+    return out
+
+
+def test_pool_equals_private_predictors():
+    """Idle session, undo, prev_masks (dropped on the first click under the cascade rule, used later)."""
+    make = lambda: _predictor(cascade_step=1, cascade_clicks=1)
+    pool = SessionPool(make(), max_sessions=4, pred_thr=PRED_THR)
+    a, b, c = twins = _twins(pool, make)
+    g = torch.Generator().manual_seed(0)
+    # click 1, with a prev_mask for a: the cascade rule drops it (len(clicks) <= cascade_clicks)
+    for t in twins:
+        t.add(True, t.centre)
+    dropped = torch.rand(1, 1, a.pred.original_image.shape[2], a.pred.original_image.shape[3], generator=g)
+    before = pool.readbacks
+    res = step(twins, {a: dropped})
+    assert pool.readbacks == before + 1
+    assert_equal(twins, res, "click 1")
+    ref = _predictor(cascade_step=1, cascade_clicks=1)         # the same click without the mask gives the same map
+    ref.set_input_image(blob_image(*SIZES[0], seed=0)[0])
+    assert np.array_equal(ref.get_prediction(a.clicker), res[a.sid][1])
+    # click 2: b idles and keeps its state
+    held = pool.probs(b.sid).clone()
+    a.add(False, (3, 5))
+    c.add(True, (c.centre[0] + 6, c.centre[1] - 4))
+    res = step([a, c])
+    assert_equal([a, c], res, "click 2")
+    assert torch.equal(pool.probs(b.sid), held) and torch.equal(held, b.pred.prev_prediction)
+    # click 3 on all, then a takes it back and clicks elsewhere
+    saved = a.save()
+    a.add(True, (a.centre[0] - 8, a.centre[1] + 9))
+    b.add(False, (40, 6))
+    c.add(False, (2, 60))
+    res = step(twins)
+    assert_equal(twins, res, "click 3")
+    undone = res[a.sid][1].copy()
+    a.restore(saved)
+    assert torch.equal(pool.probs(a.sid), a.pred.prev_prediction)
+    a.add(False, (50, 70))
+    res = step([a])
+    assert_equal([a], res, "click 3 after undo")
+    assert len(a.clicker) == 3 and not np.array_equal(res[a.sid][1], undone)
+    # click 4 with a prev_mask for b (its third click: used) and none for the others
+    used = torch.rand(1, 1, 48, 48, generator=g)
+    for t in twins:
+        t.add(True, (t.centre[0] + 2, t.centre[1] + 3))
+    res = step(twins, {b: used})
+    assert_equal(twins, res, "click 4")
+    assert pool.readbacks == before + 5
+    assert isinstance(pool.probs(b.sid), torch.Tensor) and tuple(pool.probs(b.sid).shape) == (1, 1, 48, 48)
+
+
+def test_prev_mask_changes_the_map_when_it_is_used():
+    """The second half of the prev_masks checkpoint: past the cascade clicks the caller's map is what the network sees."""
+    make = lambda: _predictor(cascade_step=1, cascade_clicks=1)
+    pool = SessionPool(make(), max_sessions=2)
+    image, centre = blob_image(48, 48, seed=1)
+    with_mask, without = Twin(pool, make, image), Twin(pool, make, image)
+    for t in (with_mask, without):
+        t.add(True, centre)
+    assert_equal([with_mask, without], step([with_mask, without]), "click 1")
+    for t in (with_mask, without):
+        t.add(False, (4, 40))
+    res = step([with_mask, without], {with_mask: torch.rand(1, 1, 48, 48, generator=torch.Generator().manual_seed(3))})
+    assert_equal([with_mask, without], res, "click 2")
+    assert not torch.equal(pool.probs(with_mask.sid), pool.probs(without.sid))
+    with pytest.raises(ValueError):
+        pool.predict({with_mask.sid: with_mask.clicker}, prev_masks={without.sid: torch.zeros(1, 1, 48, 48)})
+
+
+def test_net_clicks_limit():
+    make = lambda: _predictor(net_clicks_limit=2)
+    pool = SessionPool(make(), max_sessions=3)
+    twins = _twins(pool, make)
+    script = [[(True, 0, 0), (True, 5, -6), (False, -20, 10), (True, -7, 3)],
+              [(True, 0, 0), (False, 15, 15)],
+              [(False, -20, -30), (True, 0, 0), (False, 20, 30), (False, 22, -20), (True, 4, 4)]]
+    for k in range(5):
+        live = [t for t, sc in zip(twins, script) if k < len(sc)]
+        for t, sc in zip(twins, script):
+            if k < len(sc):
+                t.add(sc[k][0], (t.centre[0] + sc[k][1], t.centre[1] + sc[k][2]))
+        assert_equal(live, step(live), f"click {k + 1}")
+    assert pool.pred.get_points_nd([t.clicker.get_clicks() for t in twins]).shape[1] == 4
+
+
+def test_recalculation_reruns_the_session_inside_the_call():
+    """skip_clicks=0: the first click runs on the whole image; where the predicted box covers less than half of it the
+    click runs again zoomed in, in a second forward for those sessions only (two read-backs instead of one)."""
+    make = lambda: _predictor(skip_clicks=0)
+    pool = SessionPool(make(), max_sessions=3)
+    small = _twins(pool, make, sizes=[(60, 80), (48, 48)], radius=0.15)
+    large = _twins(pool, make, sizes=[(48, 48)], radius=0.45)[0]
+    twins = small + [large]
+    for t in twins:
+        t.add(True, t.centre)
+    res = step(twins)
+    assert (pool.readbacks, pool.forwards) == (2, 3)     # round 1: sizes (60, 80) and (48, 48); round 2: the small ones, zoomed
+    assert_equal(twins, res, "click 1")
+    assert small[0].pred.zoom_in._object_roi is not None and large.pred.zoom_in._object_roi is None
+    for t in twins:
+        t.add(False, (1, 2))
+    res = step(twins)
+    assert pool.readbacks == 3
+    assert_equal(twins, res, "click 2")
+
+
+def test_slots_and_errors():
+    pool = SessionPool(_predictor(), max_sessions=3)
+    images = [blob_image(20 + 4 * j, 24, seed=j)[0] for j in range(4)]
+    sids = [pool.open(im) for im in images[:3]]
+    assert sids == [0, 1, 2]
+    with pytest.raises(ValueError):
+        pool.open(images[3])
+    pool.predict({1: [Click(True, (10, 10), 0)]})
+    assert float(pool.probs(1).max()) > 0.5
+    pool.close(1)
+    with pytest.raises(KeyError):
+        pool.probs(1)
+    with pytest.raises(KeyError):
+        pool.predict({1: [Click(True, (10, 10), 0)]})
+    assert pool.open(images[3]) == 1                        # the freed slot, with a fresh state
+    assert tuple(pool.probs(1).shape) == (1, 1, 32, 24) and float(pool.probs(1).abs().max()) == 0.0
+    assert pool.get_states(1)["roi"] is None and pool.get_states(1)["box"] is None
+    with pytest.raises(ValueError):
+        SessionPool(_predictor(max_size=40))
+    with pytest.raises(ValueError):
+        SessionPool(get_predictor(StubNet(), "NoBRS", "cpu", zoom_in_params=dict(target_size=32)))
+
+
+def test_chunked_equals_unchunked():
+    sizes = [(48, 48), (60, 80), (48, 48), (48, 48), (50, 70)]
+    pools = [SessionPool(_predictor(), max_sessions=5, max_batch=mb) for mb in (5, 2)]
+    sids = [[p.open(blob_image(H, W, seed=j)[0]) for j, (H, W) in enumerate(sizes)] for p in pools]
+    assert sids[0] == sids[1]
+    clicks = {sid: [Click(True, (H // 2, W // 2), 0)] for sid, (H, W) in zip(sids[0], sizes)}
+    for k in range(3):
+        outs = [p.predict(clicks) for p in pools]
+        for sid in sids[0]:
+            assert np.array_equal(outs[0][sid], outs[1][sid]) and outs[0][sid].any()
+            assert torch.equal(pools[0].probs(sid), pools[1].probs(sid))
+        clicks = {sid: cl + [Click(k % 2 == 1, (3 + 5 * k + sid, 7 + 4 * k), k + 1)] for sid, cl in clicks.items()}
+    # every input here is zoomed to (32, 32): one forward un-chunked, three in chunks of two; one read-back per call either way
+    assert (pools[0].forwards, pools[0].readbacks) == (3, 3)
+    assert (pools[1].forwards, pools[1].readbacks) == (9, 3)
+
+
+@pytest.mark.parametrize("shape", [(8, 8), (16, 12), (5, 13), (9, 7), (3, 1), (21, 9)])
+def test_bit_codec_round_trip(shape):
+    """H * W % 64 in {0, 1, 63} (and 3, 61): layout, zero padding bits, round trip."""
+    H, W = shape
+    assert H * W % 64 in (0, 1, 63, 3, 61)
+    mask = np.random.RandomState(H * W).rand(H, W) < 0.5
+    mask[-1, -1] = True
+    words = sessions.pack_mask(mask)
+    assert words.dtype == np.uint64 and words.shape == ((H * W + 63) // 64,)
+    for i in (0, H * W // 2, H * W - 1):
+        assert bool((int(words[i >> 6]) >> (i & 63)) & 1) == bool(mask.reshape(-1)[i])
+    if H * W % 64:
+        assert int(words[-1]) >> (H * W % 64) == 0
+    assert np.array_equal(sessions.unpack_mask(words, H, W), mask)
+    assert np.array_equal(sessions.unpack_mask(words.view(np.int64), H, W), mask)       # as a read-back holds them
+    one = np.zeros((H, W), bool)
+    one.reshape(-1)[H * W - 1] = True
+    w = sessions.pack_mask(one)
+    assert int(w[(H * W - 1) >> 6]) == 1 << ((H * W - 1) & 63) and int(w.astype(object).sum()) == int(w[-1])
