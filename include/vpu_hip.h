@@ -292,6 +292,21 @@ int vpu_pue_encode(const float* points, const int32_t* boxes, const float* lut, 
 int vpu_pue_scribble_rows(const float* points, const double* vec, void* out, double* out64, int32_t B, int32_t n,
                           int32_t num_max, int32_t img, int32_t ld, int32_t dtype, void* stream);
 int vpu_draw_polyline(const int32_t* curve, float* disks, int32_t B, int32_t P, int32_t H, int32_t W, void* stream);
+/* Per-row prompt kinds (prompt type 3; an extension, not in the reference): kinds int32 [B], 0 = clicks only, 1 = box,
+ * 2 = scribble, so that one batch mixes all three.  Row by row both write what the single-type calls write for that sample
+ * alone.
+ * vpu_pue_encode_rows = vpu_pue_encode + vpu_pue_scribble_rows in one launch: a kind-0 sample as with boxes == NULL; a kind-1
+ * sample with boxes[b] (a negative slot still means "no box"); a kind-2 sample as kind 0, then its LAST valid positive row
+ * replaced by (vec[b] | one-hot 0), nothing replaced when it has no valid positive click.  boxes int32 [B][5] and vec
+ * float64 [B][2*img] are read only for the samples of their kind but must both be given; 1 <= n <= min(num_max, 64).
+ * vpu_draw_prompt_rows: into disks fp32 [B][2][H][W] (already holding the click disks) nothing (kind 0), the box outline of
+ * vpu_disk_maps (kind 1, slot >= 0; channel by slot < n) or the open poly-line of vpu_draw_polyline through the first
+ * counts[b] vertices of curve int32 [B][Pmax][2] (kind 2; counts[b] is clamped to Pmax, a count of 0 or 1 draws nothing). */
+int vpu_pue_encode_rows(const float* points, const int32_t* kinds, const int32_t* boxes, const double* vec, const float* lut,
+                        void* out, double* out64, int32_t B, int32_t n, int32_t num_max, int32_t img, int32_t ld,
+                        int32_t dtype, void* stream);
+int vpu_draw_prompt_rows(const int32_t* kinds, const int32_t* boxes, const int32_t* curve, const int32_t* counts, float* disks,
+                         int32_t B, int32_t Pmax, int32_t n, int32_t H, int32_t W, void* stream);
 /* Exact Euclidean distance transform of B masks: dist[b][y][x] = distance of a non-zero pixel to the nearest zero pixel
  * (0 at zero pixels; +inf when there is none), float32(sqrt(float64)) of the exact integer squared distance -- the map
  * whose arg-max the click simulators take (clicker.py:29-56, trainer.py:628-629, 673-674, 736-737).  zero_border != 0:

@@ -114,6 +114,8 @@ SIGNATURES = {
     "vpu_chamfer5": [_P, _P, _P, _I, _I, _I, _I, _P],
     "vpu_pue_scribble_rows": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_draw_polyline": [_P, _P, _I, _I, _I, _I, _P],
+    "vpu_pue_encode_rows": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vpu_draw_prompt_rows": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpu_mask_bbox": [_P, _F, _P, _I, _P, _I, _I, _I, _P],
     "vpu_masked_argmax": [_P, _P, _P, _I, _I, _I, _P],
     "vpu_error_masks": [_P, _P, _P, _P, _I, _I, _P],

@@ -410,6 +410,123 @@ __global__ __launch_bounds__(256) void draw_box_kernel(const int* __restrict__ b
 }
 
 // ------------------------------------------------------------------------------------------------
+// Per-row prompt kinds (prompt type 3, an extension): every sample of a batch says what it carries -- kinds[b] = 0 clicks only,
+// 1 a box (boxes[b], a negative slot still "no box"), 2 a scribble (profiles vec[b], vertex count counts[b]) -- so the
+// sessions of a pool that drew different things share one forward.  Row by row the results are those of the single-type
+// kernels above run on that sample alone.
+//
+// (1) pue_encode_kernel's rows and pue_scribble_rows_kernel's replacement in one launch, one block per output row (b, slot).
+//     The last valid positive row of a kind-2 sample is found by every wave for itself: lane i < n reads the order of
+//     positive click i, one ballot, the highest set bit -- no shared memory and no barrier, where the two-launch form walks
+//     the n slots on thread 0 in front of a barrier.  The arithmetic of a click / box row is pue_encode_kernel's, statement
+//     for statement (same translation unit, same flags: same bits).
+template <typename T>
+__global__ __launch_bounds__(256) void pue_encode_rows_kernel(const float* __restrict__ points, const int* __restrict__ kinds,
+                                                              const int* __restrict__ boxes, const double* __restrict__ vec,
+                                                              const float* __restrict__ lut, T* __restrict__ out,
+                                                              double* __restrict__ out64, int n, int num_max, int img, int ld) {
+    const int slot = blockIdx.x % (2 * num_max), b = blockIdx.x / (2 * num_max);
+    const int pol = slot / num_max, within = slot % num_max;
+    const int E = 2 * img + 3;
+    const int rk = kinds[b];
+    T* o = out + ((int64_t)b * 2 * num_max + slot) * ld;
+    double* o64 = out64 ? out64 + ((int64_t)b * 2 * num_max + slot) * E : nullptr;
+    if (rk == 2 && pol == 0 && within < n) {       // (block-uniform: only the positive rows of a scribble sample look)
+        const int lane = threadIdx.x & 63;
+        const bool valid = lane < n && points[((int64_t)b * 2 * n + lane) * 3 + 2] != -1.0f;     // n <= 64 (launcher)
+        const unsigned long long m = __ballot(valid);
+        const int row = m ? 63 - __builtin_clzll(m) : -1;
+        if (row == within) {                       // is_vpu_model.py:337-352: (x profile | y profile | one-hot 0)
+            const double* v = vec + (int64_t)b * 2 * img;
+            for (int j = threadIdx.x; j < ld; j += 256) {
+                double x = 0.0;
+                if (j < 2 * img) x = v[j];
+                else if (j == 2 * img) x = 1.0;
+                o[j] = from_f32<T>((float)x);
+                if (o64 && j < E) o64[j] = x;
+            }
+            return;
+        }
+    }
+    const int* bx = rk == 1 ? boxes + b * 5 : nullptr;
+    // kind: 0 not-a-point, 1 click, 2 box
+    int kind = 0, x = 0, y = 0, rx = 9, ry = 9, sx = 3, sy = 3, label = pol;
+    bool empty = false;
+    if (within < n) {
+        const int i = pol * n + within;
+        const float* p = points + ((int64_t)b * 2 * n + i) * 3;
+        if (p[2] != -1.0f) {
+            kind = 1;
+            x = (int)p[0];
+            y = (int)p[1];
+        }
+        if (bx && bx[4] == i) {
+            kind = 2;
+            x = bx[0]; y = bx[1];
+            label = i < n ? 0 : 1;
+            const int w = bx[2], h = bx[3];
+            if (bx[0] + bx[1] + w + h == 0) empty = true;
+            const int kw = fdiv(w, 2) * 2 - 1, kh = fdiv(h, 2) * 2 - 1;
+            rx = fdiv(kw - 1, 2); ry = fdiv(kh - 1, 2);
+            sx = fdiv(rx, 3); sy = fdiv(ry, 3);
+            if (sx == 0 || sy == 0) empty = true;
+        }
+        if (kind != 0 && !empty) {
+            const int ulx = x - rx, uly = y - ry, brx = x + rx + 1, bry = y + ry + 1;
+            if (!in_img(ulx, uly, img, img) && !in_img(brx, bry, img, img)) empty = true;
+        }
+    }
+    for (int j = threadIdx.x; j < ld; j += 256) {
+        float v = 0.f;
+        if (kind == 0) {
+            v = (j == E - 1) ? 1.f : 0.f;
+        } else if (j < 2 * img) {
+            if (!empty) {
+                const bool isx = j < img;
+                const int pos = isx ? j : j - img;
+                const int c = isx ? x : y, r = isx ? rx : ry, s = isx ? sx : sy;
+                const int d = pos - c;
+                if (d >= -r && d <= r) {
+                    if (kind == 1) v = lut[d + 9];
+                    else v = expf(-((float)(d * d)) / (float)(2 * s * s));
+                }
+            }
+        } else if (j < E) {
+            v = (j - 2 * img == label) ? 1.f : 0.f;
+        }
+        o[j] = from_f32<T>(v);
+        if (o64 && j < E) o64[j] = (double)v;
+    }
+}
+
+// (2) draw_box_kernel's outline or draw_polyline_kernel's open poly-line, per sample, in one launch: grid (max(Pmax - 1, 4), B),
+//     block (seg, b).  curve int32 [B][Pmax][2] is padded; counts[b] vertices of row b are read (clamped to Pmax), so a kind-2
+//     row draws counts[b] - 1 segments and a count of 0 or 1 draws nothing.  A block beyond its row's work returns before any
+//     barrier; the decision reads only per-row scalars, so it is block-uniform.  Segment flags as in the two kernels above.
+__global__ __launch_bounds__(256) void draw_prompt_rows_kernel(const int* __restrict__ kinds, const int* __restrict__ boxes,
+                                                               const int* __restrict__ curve, const int* __restrict__ counts,
+                                                               float* __restrict__ disks, int Pmax, int n, int H, int W) {
+    __shared__ TlSeg sg;
+    const int seg = blockIdx.x, b = blockIdx.y;
+    const int rk = kinds[b];
+    if (rk == 1) {
+        const int* bx = boxes + b * 5;
+        if (seg >= 4 || bx[4] < 0) return;
+        const int ch = bx[4] < n ? 0 : 1;
+        const int hw = fdiv(bx[2], 2), hh = fdiv(bx[3], 2);
+        const int x0 = bx[0] - hw, x1 = bx[0] + hw, y0 = bx[1] - hh, y1 = bx[1] + hh;
+        const int cx[4] = {x0, x1, x1, x0}, cy[4] = {y0, y0, y1, y1};
+        const int j = (seg + 3) & 3;
+        tl_draw_segment(sg, cx[j], cy[j], cx[seg], cy[seg], 2, disks + ((int64_t)b * 2 + ch) * H * W, H, W);
+    } else if (rk == 2) {
+        const int P = min(counts[b], Pmax);
+        if (seg + 1 >= P) return;
+        const int* c = curve + ((int64_t)b * Pmax + seg) * 2;
+        tl_draw_segment(sg, c[0], c[1], c[2], c[3], seg == 0 ? 3 : 2, disks + (int64_t)b * 2 * H * W, H, W);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // NoBRS loop bookkeeping on the device (isegm/inference/transforms/zoom_in.py:30-165, isegm/inference/clicker.py:29-56):
 // the previous prediction never leaves the GPU; these two reductions replace the host passes over it.
 // (1) bounding box of {prob > thr} joined with the positive clicks (the reference sets those pixels in a copy of the mask
@@ -691,6 +808,36 @@ extern "C" int vpu_draw_polyline(const int32_t* curve, float* disks, int32_t B, 
     if (P < 2) return VPU_OK;        // (PolyLine draws segments: a single point draws nothing)
     draw_polyline_kernel<<<dim3((unsigned)(P - 1), (unsigned)B), 256, 0, ST>>>(curve, disks, P, H, W);
     return vpu_check_launch("vpu_draw_polyline");
+}
+
+extern "C" int vpu_pue_encode_rows(const float* points, const int32_t* kinds, const int32_t* boxes, const double* vec,
+                                   const float* lut, void* out, double* out64, int32_t B, int32_t n, int32_t num_max,
+                                   int32_t img, int32_t ld, int32_t dtype, void* stream) {
+    vpu_clear_stale_error();
+    if (!points || !kinds || !boxes || !vec || !lut || !out || n > num_max || n > 64 || n < 1 || ld < 2 * img + 3 || B <= 0) {
+        vpu_set_error("pue_encode_rows: non-null operands, 1 <= n <= min(num_max, 64), ld >= 2*img+3");
+        return VPU_ERR_ARG;
+    }
+    const unsigned grid = (unsigned)(B * 2 * num_max);
+    if (dtype == VPU_BF16)
+        pue_encode_rows_kernel<bf16_t><<<grid, 256, 0, ST>>>(points, kinds, boxes, vec, lut, (bf16_t*)out, out64, n, num_max, img, ld);
+    else if (dtype == VPU_F32)
+        pue_encode_rows_kernel<float><<<grid, 256, 0, ST>>>(points, kinds, boxes, vec, lut, (float*)out, out64, n, num_max, img, ld);
+    else { vpu_set_error("pue_encode_rows: dtype"); return VPU_ERR_ARG; }
+    return vpu_check_launch("vpu_pue_encode_rows");
+}
+
+extern "C" int vpu_draw_prompt_rows(const int32_t* kinds, const int32_t* boxes, const int32_t* curve, const int32_t* counts,
+                                    float* disks, int32_t B, int32_t Pmax, int32_t n, int32_t H, int32_t W, void* stream) {
+    vpu_clear_stale_error();
+    if (!kinds || !boxes || !curve || !counts || !disks || B <= 0 || B > 65535 || Pmax <= 0 || Pmax > 65535 || n <= 0 || H <= 0 ||
+        W <= 0) {
+        vpu_set_error("draw_prompt_rows: non-null operands, sizes");
+        return VPU_ERR_ARG;
+    }
+    const unsigned segs = (unsigned)(Pmax - 1 > 4 ? Pmax - 1 : 4);
+    draw_prompt_rows_kernel<<<dim3(segs, (unsigned)B), 256, 0, ST>>>(kinds, boxes, curve, counts, disks, Pmax, n, H, W);
+    return vpu_check_launch("vpu_draw_prompt_rows");
 }
 
 extern "C" int vpu_mask_bbox(const float* prob, float thr, const int32_t* pos_clicks, int32_t nclicks, int32_t* out, int32_t B,

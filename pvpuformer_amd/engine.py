@@ -975,7 +975,7 @@ class Engine:
 
     # ------------------------------------------------------------------------------------------ model
     def forward(self, image4, points, boxes=None, prompt_type=0, drop_mask=None, training=False, taps=None,
-                materialize_aux=True, scribble=None, coord_override=None, prenorm=False):
+                materialize_aux=True, scribble=None, coord_override=None, prenorm=False, kinds=None):
         """image4 fp32 [B,4,H,W]; points fp32 [B,2n,3]; boxes int32 [B,5] (prompt_type 1); scribble (prompt_type 2) =
         (curve int32 [B,P,2] poly-line vertices, profiles float64 [B, 2*img] from isegm/model/scribble.py).
         A box row with a negative slot, (0, 0, 0, 0, -1), marks a sample without a box: it is computed exactly as under
@@ -985,7 +985,10 @@ class Engine:
         [B,S,h,w] for the fused loss (ops.p2cl_up_fwd_bwd) and backward() takes their gradient as ``d_sim_low``.
         ``coord_override`` fp32 [B,2,H,W]: the two click-map channels of the coordinate features as the CALLER made them
         (no disk maps / outlines are drawn); ``prenorm``: the rgb planes of image4 are normalised already -- both for the
-        public ``backbone_forward`` (is_vpu_model.py:383-419)."""
+        public ``backbone_forward`` (is_vpu_model.py:383-419).
+        prompt_type 3 (an extension, inference only): a prompt kind per sample, ``kinds`` int32 [B] (0 clicks only, 1 box,
+        2 scribble), with boxes int32 [B,5] and scribble = (curve int32 [B,Pmax,2] padded, counts int32 [B] vertices per
+        sample, profiles float64 [B, 2*img]); each sample is computed as under the prompt type of its kind."""
         assert image4.is_cuda and image4.dtype == torch.float32 and image4.is_contiguous()
         if not self.shadow_valid:
             self.refresh_weights()
@@ -1004,12 +1007,21 @@ class Engine:
         self._token_rows = B * NT     # the reduction length of the ViT blocks' weight gradients (the packed queue)
         n = points.shape[1] // 2
         points = self._upload(points, torch.float32)
-        boxes = self._upload(boxes, torch.int32) if prompt_type == 1 else None
-        curve = prof = None
+        boxes = self._upload(boxes, torch.int32) if prompt_type in (1, 3) else None
+        curve = prof = rows = None
         if prompt_type == 2:
             curve = self._upload(scribble[0], torch.int32)
             prof = self._upload(scribble[1], torch.float64)
             assert curve.shape[0] == B and tuple(prof.shape) == (B, 2 * self.img)
+        elif prompt_type == 3:
+            if training:
+                raise RuntimeError("prompt_type 3 (a prompt kind per sample) is inference-only")
+            curve = self._upload(scribble[0], torch.int32)
+            prof = self._upload(scribble[2], torch.float64)
+            rows = (self._upload(kinds, torch.int32), self._upload(scribble[1], torch.int32))      # (kinds, vertex counts)
+            assert curve.dim() == 3 and curve.shape[0] == B and curve.shape[1] >= 1 and curve.shape[2] == 2
+            assert tuple(prof.shape) == (B, 2 * self.img) and tuple(boxes.shape) == (B, 5)
+            assert tuple(rows[0].shape) == (B,) and tuple(rows[1].shape) == (B,)
         prompts = (points, boxes, curve, prof)
         # round 5, two lanes: the prompt tokens' side of the DMA neck on its own stream (_neck_two_lane).  What needs the
         # prompts only -- the PuE vectors, their MLP, layer 0's token self-attention -- is launched now, beside the backbone;
@@ -1019,7 +1031,7 @@ class Engine:
         if lanes and self._tok_stream is None:
             self._tok_stream = torch.cuda.Stream(device=self.dev)
         cx = SimpleNamespace(B=B, H=H, W=W_, g=g, wside=wside, nw_side=nw_side, NT=NT, M=B * NT, n=n, nq=2 * self.nmax,
-                             training=training, taps=taps, T=self._tok_stream if lanes else None)
+                             training=training, taps=taps, T=self._tok_stream if lanes else None, rows=rows)
         started = self._start_token_lane(cx, prompts) if lanes and self.neck_lanes != 3 else None
         x = self._embed(cx, image4, prompts, pos_win, coord_override, prenorm)
         xr = self._blocks(cx, x)
@@ -1044,9 +1056,13 @@ class Engine:
             assert tuple(disks.shape) == (B, 2, H, W_)
         else:
             disks = self._new(B, 2, H, W_, dtype=torch.float32)
-            ops.disk_maps(points, boxes, disks, B, cx.n, H, W_, self.norm_radius)
-            if curve is not None:     # ISModel.draw_scribble (is_model.py:123-146): poly-line into the positive channel
-                ops.draw_polyline(curve, disks, B, curve.shape[1], H, W_)
+            if cx.rows is not None:   # prompt type 3: the click disks, then per sample nothing / the outline / the poly-line
+                ops.disk_maps(points, None, disks, B, cx.n, H, W_, self.norm_radius)
+                ops.draw_prompt_rows(cx.rows[0], boxes, curve, cx.rows[1], disks, B, curve.shape[1], cx.n, H, W_)
+            else:
+                ops.disk_maps(points, boxes, disks, B, cx.n, H, W_, self.norm_radius)
+                if curve is not None:     # ISModel.draw_scribble (is_model.py:123-146): poly-line into the positive channel
+                    ops.draw_polyline(curve, disks, B, curve.shape[1], H, W_)
         if cx.taps is not None:
             cx.taps["disks"] = disks
         KP = 2 * self.k3p
@@ -1127,9 +1143,12 @@ class Engine:
         B, n, nq = cx.B, cx.n, cx.nq
         points, boxes, _, prof = prompts
         pue = Var(self._new(B * nq, self.Epad))
-        ops.pue_encode(points, boxes, self.lut, pue.t, None, B, n, self.nmax, self.img, self.Epad)
-        if prof is not None:     # _guassinvector_scribble (is_vpu_model.py:294-352): the last valid positive row becomes the scribble
-            ops.pue_scribble_rows(points, prof, pue.t, None, B, n, self.nmax, self.img, self.Epad)
+        if cx.rows is not None:  # prompt type 3: click, box and scribble samples in one launch
+            ops.pue_encode_rows(points, cx.rows[0], boxes, prof, self.lut, pue.t, None, B, n, self.nmax, self.img, self.Epad)
+        else:
+            ops.pue_encode(points, boxes, self.lut, pue.t, None, B, n, self.nmax, self.img, self.Epad)
+            if prof is not None:     # _guassinvector_scribble (is_vpu_model.py:294-352): the last valid positive row becomes the scribble
+                ops.pue_scribble_rows(points, prof, pue.t, None, B, n, self.nmax, self.img, self.Epad)
         return self.mlp(pue, "neck.ffn_layer.lin1", "neck.ffn_layer.lin2", B * nq, self.Epad, 2048, self.D, "relu",
                         w1=self.w_lin1p, k_grad=self.E, x_grad=False)
 

@@ -16,14 +16,25 @@ common count by ``get_points_nd`` with not-a-point rows that it ignores.  In the
 sequential ones bit for bit.  ``check_possible_recalculation`` is honoured inside the call: the sessions it fires for run a
 second forward of their own, as ``get_prediction`` re-runs itself.
 
-Click prompts only (there is no ground truth to derive boxes from).  On a CPU device the same scheduler runs with torch /
-numpy stand-ins of the two kernels (``_HostOps``), which is what the CPU tests check it with."""
+Drawn prompts.  Besides its clicks a session may hand ``predict`` a box or a stroke that the annotator drew (no ground
+truth is involved: deriving prompts from one is ``BatchedEvaluator``'s job).  The drawn coordinates are image pixels; the
+host maps them into the network's frame with the map ``ZoomIn.transform`` applies to that session's clicks (``map_drawn``),
+truncates them to integers and mirrors the columns for the flip row, then states the box row (``box_row``: ``cal_box``'s
+un-jittered arithmetic) or the stroke's curve, rectangle and profiles (``stroke_row``).  A forward whose rows are all clicks
+is the plain call, one with clicks and boxes is ``as_prompt_type=1`` with the no-box row (0, 0, 0, 0, -1), one that holds a
+stroke is ``as_prompt_type=3`` (a prompt kind per row, ``is_vpu_model.forward``): still one forward per network input size.
+The new kernels run inside the network, so the pool needs no further device operation of its own.
+
+On a CPU device the same scheduler runs with torch / numpy stand-ins of the two kernels (``_HostOps``), which is what the
+CPU tests check it with."""
 import ctypes as C
+import random
 
 import numpy as np
 import torch
 
-from .batched import BatchedEvaluator, _load_image, batchable
+from ..model.scribble import scribble_profiles
+from .batched import BatchedEvaluator, _load_image, _padded_slot, batchable
 from .transforms import AddHorizontalFlip, Roi, ZoomIn
 
 _REC = 4             # int64 per session record (int32 [8]: area, count, rmin, rmax, cmin, cmax, 0, 0)
@@ -69,10 +80,52 @@ def host_session_paste(prob_map, H, W, roi, pred_thr, box_thr):
     return canvas, pack_mask(mask), np.array([int(mask.sum())] + box + [0, 0], dtype=np.int32)
 
 
+# ------------------------------------------------------------------------------------------------------ drawn prompts
+def map_drawn(points, roi, size, mirror):
+    """Image pixels ``points`` [P, 2] of (row, col) -> int64 [P, 2] of (x, y) in the network input of ``size`` cropped from
+    ``roi``: ``Roi.to_crop``'s expression (the map of the session's clicks; the identity on integer pixels when the whole image
+    goes in unscaled), truncation toward zero as ``scribble_curves`` / ``cal_box`` truncate, then for the flip row the mirror
+    ``size_w - 1 - col`` of the click lists.  Points outside the roi map outside the input; the kernels clip."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    r0, r1, c0, c1 = roi
+    rows = (size[0] * (p[:, 0] - r0) / (r1 - r0 + 1)).astype(np.int64)
+    cols = (size[1] * (p[:, 1] - c0) / (c1 - c0 + 1)).astype(np.int64)
+    if mirror:
+        cols = size[1] - 1 - cols
+    return np.stack([cols, rows], 1)
+
+
+def own_slot(n_own):
+    """The PuE row of a drawn box in the session's own click layout (``n_own`` rows per polarity): ``cal_box``'s
+    ``as_allmask=False`` rule with the box as the missing region -- the annotator outlines the object, there is no
+    false-positive region -- which is always the LAST positive row, ``n_own - 1`` (trainer.py:1088).  A click in that row is
+    replaced by the box in the encoder (its disk is still drawn), as in the reference."""
+    return n_own - 1
+
+
+def box_row(xy, slot):
+    """``cal_box``'s un-jittered row (x_center, y_center, width, height, slot) of the mapped corners ``xy`` [2, 2] in any
+    order; a box it calls degenerate (a centre below 1 or an extent below 1) is its all-zero row."""
+    x0, x1, y0, y1 = int(xy[:, 0].min()), int(xy[:, 0].max()), int(xy[:, 1].min()), int(xy[:, 1].max())
+    xc, yc, bw, bh = int(0.5 * (x0 + x1)), int(0.5 * (y0 + y1)), x1 - x0, y1 - y0
+    if xc >= 1 and yc >= 1 and bw >= 1 and bh >= 1:
+        return (xc, yc, bw, bh, slot)
+    return (0, 0, 0, 0, 0)
+
+
+def stroke_row(xy, img, rng):
+    """(curve int32 [P, 2], profiles float64 [2 * img]) of the mapped stroke ``xy``: the curve is the points as they are, the
+    rectangle their bounding box in ``cal_scribble``'s form, the profiles ``scribble_profiles``' drawn from ``rng``."""
+    curve = np.ascontiguousarray(xy, dtype=np.int32)
+    c0, c1, r0, r1 = int(xy[:, 0].min()), int(xy[:, 0].max()), int(xy[:, 1].min()), int(xy[:, 1].max())
+    rect = np.array([[[int(0.5 * (c0 + c1)), int(0.5 * (r0 + r1)), c1 - c0, r1 - r0]]], dtype=np.int64)
+    return curve, scribble_profiles(curve[None, None], rect, img, rng=rng)[0]
+
+
 class _Session:
     """One session's state (a slot of the pool); the attribute names are the ones ``BatchedEvaluator._plan`` reads."""
 
-    def __init__(self, sid, image):
+    def __init__(self, sid, image, seed=None):
         self.sid, self.image = sid, image
         self.H, self.W = int(image.shape[1]), int(image.shape[2])
         self.canvas = [torch.zeros(self.H, self.W, device=image.device, dtype=torch.float32) for _ in range(2)]
@@ -81,6 +134,8 @@ class _Session:
         self.roi = None                # ZoomIn._object_roi
         self.box = None                # (count, r0, r1, c0, c1) of ZoomIn._probs > prob_thresh (no clicks); None: no _probs
         self.plan = None
+        self.rng = random.Random(seed)  # the stroke profiles' draws: the session's own generator
+        self.drawn = None              # the drawn prompt of the call in progress: ("box", [2, 2]) / ("stroke", [P, 2]) of (row, col)
 
 
 class _Round:
@@ -213,9 +268,11 @@ class SessionPool:
     ``batched.batchable(predictor)`` holds (ValueError otherwise).  It lends the pool its network, its transforms' parameters,
     ``get_points_nd`` / ``net_clicks_limit`` and the cascade rule for ``prev_masks``; its own image and state are not touched.
 
-    ``sid = pool.open(image)``; ``pool.predict({sid: clicks, ...}, prev_masks=None) -> {sid: bool ndarray [H, W]}``;
-    ``pool.probs(sid)``; ``pool.get_states(sid)`` / ``pool.set_states(sid, st)``; ``pool.close(sid)``.
+    ``sid = pool.open(image, seed=None)``; ``pool.predict({sid: clicks, ...}, prev_masks=None, boxes=None, strokes=None) ->
+    {sid: bool ndarray [H, W]}``; ``pool.probs(sid)``; ``pool.get_states(sid)`` / ``pool.set_states(sid, st)``;
+    ``pool.close(sid)``.
     ``max_batch``: sessions per forward (default ``max_sessions``); a size group with more runs in chunks.
+    ``max_stroke_points``: the longest stroke ``predict`` takes.
     ``readbacks`` counts the device-to-host synchronisations (one per forward round)."""
 
     # ZoomIn on the host, from the box read back with the last prediction: BatchedEvaluator's restatement of ZoomIn.transform /
@@ -223,8 +280,9 @@ class SessionPool:
     _predicted_box = BatchedEvaluator._predicted_box
     _plan = BatchedEvaluator._plan
     _wants_recalc = BatchedEvaluator._wants_recalc
+    _own_rows = BatchedEvaluator._own_rows
 
-    def __init__(self, predictor, max_sessions=8, pred_thr=0.49, max_batch=None):
+    def __init__(self, predictor, max_sessions=8, pred_thr=0.49, max_batch=None, max_stroke_points=1024):
         if not batchable(predictor):
             raise ValueError("SessionPool: the predictor's transforms are not the batched path's (batched.batchable): only "
                              "[ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip]")
@@ -232,21 +290,25 @@ class SessionPool:
             raise ValueError("SessionPool: max_sessions and max_batch must be at least 1")
         self.pred, self.max_sessions, self.pred_thr = predictor, int(max_sessions), float(pred_thr)
         self.max_batch = int(max_batch) if max_batch is not None else self.max_sessions
+        self.max_stroke_points = int(max_stroke_points)
         self.zoom = predictor.zoom_in
         self.flip = any(type(t) is AddHorizontalFlip for t in predictor.transforms)
         self.inv = [t for t in reversed(predictor.transforms) if type(t) is not ZoomIn]   # flip average, then sigmoid
         self.prev_channel = bool(getattr(predictor.net, "with_prev_mask", True))
+        size = getattr(predictor.net, "image_size", None)     # the length of the stroke profiles (the model's own image size)
+        self.prompt_img = int(size[0]) if size is not None else None
         self.device = torch.device(predictor.device)
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
         self._slots = [None] * self.max_sessions
         self.readbacks = self.forwards = 0
 
     # ---------------------------------------------------------------------------------------------- sessions
-    def open(self, image):
-        """A new session on ``image`` (``set_input_image``'s conversions) -> its id; ids of closed sessions are reused."""
+    def open(self, image, seed=None):
+        """A new session on ``image`` (``set_input_image``'s conversions) -> its id; ids of closed sessions are reused.
+        ``seed`` seeds the session's own ``random.Random``, from which the profiles of its strokes are drawn."""
         for sid, held in enumerate(self._slots):
             if held is None:
-                self._slots[sid] = _Session(sid, _load_image(image, self.device))
+                self._slots[sid] = _Session(sid, _load_image(image, self.device), seed)
                 return sid
         raise ValueError(f"SessionPool: all {self.max_sessions} sessions are open")
 
@@ -267,13 +329,15 @@ class SessionPool:
 
     def get_states(self, sid):
         s = self._session(sid)
-        return {"roi": s.roi, "box": s.box, "prev_prediction": s.canvas[s.prev].clone()}
+        return {"roi": s.roi, "box": s.box, "prev_prediction": s.canvas[s.prev].clone(), "rng": s.rng.getstate()}
 
     def set_states(self, sid, states):
         s = self._session(sid)
         prev = states["prev_prediction"]
         assert tuple(prev.shape[-2:]) == (s.H, s.W), "the state is of another image size"
         s.roi, s.box = states["roi"], states["box"]
+        if "rng" in states:
+            s.rng.setstate(states["rng"])
         s.canvas[s.prev].copy_(prev.reshape(s.H, s.W))
 
     # ---------------------------------------------------------------------------------------------- prediction
@@ -283,15 +347,64 @@ class SessionPool:
         assert value.numel() == s.H * s.W, "prev_masks: a map of another size than the session's image"
         return value.to(self.device).float().reshape(s.H, s.W).contiguous()
 
+    def _drawn(self, clicks, boxes, strokes):
+        """{sid: ("box", float64 [2, 2]) or ("stroke", float64 [P, 2])} of (row, col) after every check of ``predict``."""
+        boxes, strokes, drawn = boxes or {}, strokes or {}, {}
+        for name, given in (("boxes", boxes), ("strokes", strokes)):
+            for sid in given:
+                if sid not in clicks:
+                    raise ValueError(f"SessionPool.predict: {name} names session {sid!r}, which is not in clicks in this call")
+                if name == "strokes" and sid in boxes:
+                    raise ValueError(f"SessionPool.predict: session {sid!r} has a box and a stroke in one call; the encoder has "
+                                     "one row to give")
+        for sid, box in boxes.items():
+            pts = np.asarray(box, dtype=np.float64)
+            if pts.shape != (4,):
+                raise ValueError(f"SessionPool.predict: the box of session {sid!r} is not (r0, c0, r1, c1)")
+            drawn[sid] = ("box", pts.reshape(2, 2))
+        for sid, stroke in strokes.items():
+            pts = np.asarray(stroke, dtype=np.float64)
+            if pts.ndim != 2 or pts.shape[1] != 2 or not 2 <= len(pts) <= self.max_stroke_points:
+                raise ValueError(f"SessionPool.predict: the stroke of session {sid!r} must be [P, 2] of (row, col) with "
+                                 f"2 <= P <= {self.max_stroke_points}")
+            cl = clicks[sid]
+            if len(cl.get_clicks() if hasattr(cl, "get_clicks") else cl) == 0:
+                raise ValueError(f"SessionPool.predict: the stroke of session {sid!r} comes without a click (only a box may)")
+            if self.prompt_img is None:
+                raise ValueError("SessionPool.predict: the network does not state its image_size, which the stroke profiles need")
+            drawn[sid] = ("stroke", pts)
+        for sid, (_, pts) in drawn.items():
+            s = self._session(sid)
+            if not (np.isfinite(pts).all() and (pts >= 0).all() and (pts[:, 0] <= s.H - 1).all() and (pts[:, 1] <= s.W - 1).all()):
+                raise ValueError(f"SessionPool.predict: the drawn prompt of session {sid!r} leaves its {s.H} x {s.W} image")
+        return drawn
+
     @torch.no_grad()
-    def predict(self, clicks, prev_masks=None):
+    def predict(self, clicks, prev_masks=None, boxes=None, strokes=None):
         """``clicks``: {sid: list of Click, or a Clicker}; ``prev_masks``: {sid: map} replaces that session's previous
         prediction for this call (dropped under ``_net_input``'s cascade rule) -> {sid: bool ndarray [H, W]}, the mask
-        ``probs(sid) > pred_thr``.  Sessions that are not named are untouched."""
+        ``probs(sid) > pred_thr``.  Sessions that are not named are untouched.
+
+        ``boxes``: {sid: (r0, c0, r1, c1)}, a drawn box in image pixels, inclusive corners in any order.  ``strokes``: {sid:
+        array-like [P, 2] of (row, col)}, a drawn stroke as the tool sampled it, 2 <= P <= ``max_stroke_points``: the points
+        are used as they are, they are neither resampled nor smoothed (the poly-line through them is drawn, and each point
+        is a candidate of the profile walk).  A session named in either must be in ``clicks`` too; one named in both, or a
+        coordinate outside the image, raises ValueError.  A drawn prompt holds for this call only: the next call of the
+        session is its clicks alone unless it draws again.
+
+        A box may come with an empty click list (a stroke may not: its encoder row replaces the last positive click's).  The
+        points of a box-only call are all padding: one not-a-point row per polarity, nothing in the click maps but the
+        outline, and by the slot rule (``own_slot``) the box takes row 0.
+
+        When ZoomIn's recalculation fires, the second round maps the SAME drawn prompt under the new crop and draws the
+        stroke profiles anew from the session's generator, which goes on from where it was.  ``get_prediction`` re-runs with
+        clicks only; here the annotator's box or stroke is still the prompt, on purpose."""
+        drawn = self._drawn(clicks, boxes, strokes)
         todo, prev_of = [], {}
         for sid, cl in clicks.items():
             s = self._session(sid)
             s.clicks = list(cl.get_clicks() if hasattr(cl, "get_clicks") else cl)
+            s.drawn = drawn.get(sid)
             todo.append(s)
         for sid, value in (prev_masks or {}).items():
             if sid not in clicks:
@@ -307,7 +420,43 @@ class SessionPool:
         if again:                           # get_prediction re-runs itself, on the predictor's own previous prediction
             left = self._round(again, {}, out)
             assert not left                 # (the crop is chosen now, so the recalculation cannot fire twice)
+        for s in todo:
+            s.drawn = None
         return out
+
+    def _prompts(self, members, size, points_nd):
+        """(prompts, as_prompt_type) of a forward over ``members`` (then their flip copies): None and 0 when nobody drew, the
+        box tensor with no-box rows and 1 when only boxes were drawn, the per-row operands and 3 when a stroke was.
+        A session's profile draws happen for its row and then for its flip row, from its own generator: its result does
+        not depend on who shares the forward."""
+        kinds = [0 if s.drawn is None else 1 if s.drawn[0] == "box" else 2 for s in members]
+        if not any(kinds):
+            return None, 0
+        n, n_batch, mirrors = len(members), points_nd.shape[1] // 2, ((False, True) if self.flip else (False,))
+        rows = n * len(mirrors)
+        boxes = np.zeros((rows, 5), dtype=np.int32)
+        boxes[:, 4] = -1
+        strokes = 2 in kinds
+        if strokes:
+            pmax = max(len(s.drawn[1]) for s in members if s.drawn is not None and s.drawn[0] == "stroke")
+            curve, counts = np.zeros((rows, pmax, 2), dtype=np.int32), np.zeros(rows, dtype=np.int32)
+            profiles = np.zeros((rows, 2 * self.prompt_img), dtype=np.float64)
+        for j, (s, kind) in enumerate(zip(members, kinds)):
+            for m, mirror in enumerate(mirrors):
+                if kind == 0:
+                    continue
+                row, xy = m * n + j, map_drawn(s.drawn[1], s.plan[0], size, mirror)
+                if kind == 1:
+                    n_own = self._own_rows(s.clicks)
+                    boxes[row] = box_row(xy, _padded_slot(own_slot(n_own), n_own, n_batch))
+                else:
+                    curve[row, :len(xy)], profiles[row] = stroke_row(xy, self.prompt_img, s.rng)
+                    counts[row] = len(xy)
+        boxes = torch.from_numpy(boxes)
+        if not strokes:
+            return (points_nd, boxes, None), 1
+        kinds = torch.tensor(kinds * len(mirrors), dtype=torch.int32)
+        return (points_nd, boxes, (torch.from_numpy(curve), torch.from_numpy(counts), torch.from_numpy(profiles)), kinds), 3
 
     def _round(self, todo, prev_of, out):
         """One forward round of ``todo`` (one forward per network input size and chunk, one read-back); fills ``out`` for
@@ -337,7 +486,12 @@ class SessionPool:
             lists = [s.plan[2] for s in members]
             if self.flip:
                 lists = lists + [[c.copy(coords=(c.coords[0], size[1] - c.coords[1] - 1)) for c in cl] for cl in lists]
-            logits = self.pred.net(image_nd, self.pred.get_points_nd(lists).float())['instances']
+            points_nd = self.pred.get_points_nd(lists).float()
+            prompts, ptype = self._prompts(members, size, points_nd)
+            if ptype == 0:
+                logits = self.pred.net(image_nd, points_nd)['instances']
+            else:
+                logits = self.pred.net(image_nd, points_nd, prompts, ptype)['instances']
             self.forwards += 1
             if tuple(logits.shape[2:]) != tuple(image_nd.shape[2:]):
                 from .transforms import resize_align_corners

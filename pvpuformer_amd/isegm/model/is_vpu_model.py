@@ -178,9 +178,27 @@ class VitMultiGaussianVector_ed_Model(ISModel):
         Extension (not in the reference): with ``as_prompt_type=1`` a row ``boxes[b] = (0, 0, 0, 0, -1)`` (any negative
         slot) says that sample b carries no box; it is computed exactly as under ``as_prompt_type=0``.  ``cal_box`` never
         produces a negative slot, and an all-zero row keeps its reference meaning (it replaces slot 0 and draws the
-        degenerate rectangle at the origin).  The batched evaluation uses it to run click and box rows in one forward."""
+        degenerate rectangle at the origin).  The batched evaluation uses it to run click and box rows in one forward.
+
+        Extension (not in the reference): ``as_prompt_type=3`` is "a prompt kind per sample".  ``prompts = (points, boxes,
+        (curve, counts, profiles), kinds)`` with kinds int32 [B] (0 clicks only, 1 box, 2 scribble), boxes int32 [B,5],
+        curve int32 [B,Pmax,2] poly-line vertices (x, y) padded to Pmax, counts int32 [B] vertices per sample, profiles
+        float64 [B, 2*img].  The operands are in the engine's form already (``isegm/model/scribble.py`` makes curves and
+        profiles), so nothing is drawn from ``random`` in here.  Sample b is computed exactly as under the prompt type of
+        its kind; boxes / curve / profiles are read only for the samples of their kind.  Inference only: it raises under
+        grad, and it is never replayed from a captured graph."""
         eng = self._ensure_engine()
-        points, boxes, scribble = self._unpack_prompts(points, prompts, as_prompt_type, edloss)
+        kinds = None
+        if as_prompt_type == 3:
+            if torch.is_grad_enabled():
+                raise RuntimeError("as_prompt_type=3 (a prompt kind per sample) is inference-only: call it under torch.no_grad()")
+            if not edloss:
+                raise NotImplementedError("edloss=False (plain head.forward) is not used by the VPU trainer / predictor")
+            points, boxes, scribble, kinds = prompts
+            scribble = tuple(torch.as_tensor(v) for v in scribble)
+            boxes, kinds = torch.as_tensor(boxes), torch.as_tensor(kinds)
+        else:
+            points, boxes, scribble = self._unpack_prompts(points, prompts, as_prompt_type, edloss)
         image = image.contiguous().float()
         if not self.weights_frozen or not eng.shadow_valid:
             eng.refresh_weights()
@@ -193,7 +211,8 @@ class VitMultiGaussianVector_ed_Model(ISModel):
         elif self.graph_inference and self.weights_frozen and drop_mask is None and image.is_cuda and scribble is None:
             inst, aux = self._graph_forward(eng, image, points, boxes, as_prompt_type)
         else:
-            inst, aux = eng.forward(image, points, boxes, as_prompt_type, drop_mask, training=False, scribble=scribble)
+            inst, aux = eng.forward(image, points, boxes, as_prompt_type, drop_mask, training=False, scribble=scribble,
+                                    kinds=kinds)
         return {'instances': inst, 'instances_aux': aux if self.with_aux_output else None}
 
     def _graph_forward(self, eng, image, points, boxes, ptype):

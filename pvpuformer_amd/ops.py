@@ -410,6 +410,18 @@ def draw_polyline(curve_i32, disks, B, P, H, W):
     _lib.call("vpu_draw_polyline", ptr(curve_i32), ptr(disks), B, P, H, W, _stream())
 
 
+def pue_encode_rows(points, kinds_i32, boxes, vec64, lut, out, out64, B, n, num_max, img, ld):
+    """``pue_encode`` and ``pue_scribble_rows`` in one launch with a prompt kind per sample (0 clicks, 1 box, 2 scribble)."""
+    _lib.call("vpu_pue_encode_rows", ptr(points), ptr(kinds_i32), ptr(boxes), ptr(vec64), ptr(lut), ptr(out), ptr(out64),
+              B, n, num_max, img, ld, code_of(out), _stream())
+
+
+def draw_prompt_rows(kinds_i32, boxes, curve_i32, counts_i32, disks, B, Pmax, n, H, W):
+    """Per sample nothing, the box outline or the open poly-line through the first ``counts[b]`` vertices of ``curve``."""
+    _lib.call("vpu_draw_prompt_rows", ptr(kinds_i32), ptr(boxes), ptr(curve_i32), ptr(counts_i32), ptr(disks), B, Pmax, n,
+              H, W, _stream())
+
+
 def mask_bbox(prob, thr, pos_clicks=None):
     """{count, rmin, rmax, cmin, cmax} (int32 [B,5], on the device) of prob[b] > thr joined with the positive clicks
     ``pos_clicks`` (int32 [n,2] (row, col) device tensor or None); prob: fp32 [B,H,W] contiguous."""

@@ -12,7 +12,14 @@ share of the time spent in the model forward (a second pass with the forward syn
 profiler pass of its own the device-to-host copies and bytes per click.  Then the time per launch (device events around a replayed graph) of
 ``vpu_session_paste_batched`` in both forms beside ``vpu_roi_paste_batched`` on the same canvases and maps, alternated.
 Prints one JSON line and writes it to ``--out`` (default profiles/sessions.json).
-usage: python tools/bench_sessions.py [--sessions N] [--clicks C] [--out FILE] [--kernels-only] [K ...]"""
+
+``--prompts box-first | mixed``: drawn prompts on every session's FIRST call (``SessionPool.predict(boxes=, strokes=)``), clicks
+afterwards -- ``box-first``: every session draws the box around its object; ``mixed``: a third of the sessions a box, a third
+a stroke through the object, a third clicks only.  The yardstick is the click-only pool on the same sessions in the same
+process (``pool_kK``, as without the option); the drawn runs are ``pool_kK_<prompts>``.  Same columns, plus the forwards per
+round (a round ends in one read-back; 1.0 = one forward per network input size, as the click-only round).  Default ``--out``
+then: profiles/sessions_prompts.json.
+usage: python tools/bench_sessions.py [--sessions N] [--clicks C] [--prompts P] [--out FILE] [--kernels-only] [K ...]"""
 import argparse
 import json
 import os
@@ -48,7 +55,26 @@ def make_sessions(n, clicks):
         rs = np.random.RandomState(i)
         script = [(True,) + first] + [(bool(k % 2 == 0), int(rs.randint(H)), int(rs.randint(W))) for k in range(1, clicks)]
         out.append((image, script))
+        # what an annotator would draw on this object: the box around it, a 64-point stroke along its diagonal
+        r0, r1, c0, c1 = (int(rows.min()), int(rows.max()), int(cols.min()), int(cols.max())) if len(rows) else (H // 4, H // 2, W // 4, W // 2)
+        t = np.linspace(0.0, 1.0, 64)
+        DRAWN[id(image)] = ((r0, c0, r1, c1), np.stack([r0 + t * (r1 - r0), c0 + t * (c1 - c0)], 1).astype(np.int64))
     return out
+
+
+DRAWN = {}           # id(image) -> (box, stroke) of make_sessions' sessions
+
+
+def drawn_on_first_call(sids, data, prompts):
+    """(boxes, strokes) of ``predict`` for the first call of these sessions under ``--prompts``."""
+    boxes, strokes = {}, {}
+    for sid, (image, _) in zip(sids, data):
+        kind = {"clicks": 2, "box-first": 0, "mixed": sid % 3}[prompts]
+        if kind == 0:
+            boxes[sid] = DRAWN[id(image)][0]
+        elif kind == 1:
+            strokes[sid] = DRAWN[id(image)][1]
+    return boxes or None, strokes or None
 
 
 def run_sequential(mk, data, clicks):
@@ -67,10 +93,11 @@ def run_sequential(mk, data, clicks):
     return masks
 
 
-def run_pool(mk, data, clicks, K):
-    """The same clicks, K sessions per ``predict`` call -> the masks of the last click."""
+def run_pool(mk, data, clicks, K, prompts="clicks", stats=None):
+    """The same clicks, K sessions per ``predict`` call -> the masks of the last click.  ``prompts``: what the sessions draw on
+    their first call; ``stats``: a dict that receives the pool's forwards and rounds."""
     pool = sessions.SessionPool(mk(), max_sessions=len(data), pred_thr=PRED_THR, max_batch=K)
-    sids = [pool.open(image) for image, _ in data]
+    sids = [pool.open(image, seed=i) for i, (image, _) in enumerate(data)]
     lists = {sid: [] for sid in sids}
     masks = None
     for k in range(clicks):
@@ -78,8 +105,15 @@ def run_pool(mk, data, clicks, K):
         for sid, (_, script) in zip(sids, data):
             lists[sid].append(Click(script[k][0], script[k][1:], k))
         for at in range(0, len(sids), K):
-            got.update(pool.predict({sid: lists[sid] for sid in sids[at:at + K]}))
+            part = sids[at:at + K]
+            if k == 0 and prompts != "clicks":
+                boxes, strokes = drawn_on_first_call(part, data[at:at + K], prompts)
+                got.update(pool.predict({sid: lists[sid] for sid in part}, boxes=boxes, strokes=strokes))
+            else:
+                got.update(pool.predict({sid: lists[sid] for sid in part}))
         masks = [got[sid] for sid in sids]
+    if stats is not None:
+        stats.update(forwards=pool.forwards, rounds=pool.readbacks)
     return masks
 
 
@@ -202,10 +236,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sessions", type=int, default=8)
     ap.add_argument("--clicks", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sessions.json"))
+    ap.add_argument("--prompts", choices=["clicks", "box-first", "mixed"], default="clicks",
+                    help="what the sessions draw on their first call (the click-only pool is always run beside it)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--kernels-only", action="store_true", help="only the paste kernels' time per launch")
     ap.add_argument("ks", nargs="*", type=int)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sessions.json" if args.prompts == "clicks" else "sessions_prompts.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_sessions: needs a GPU (nothing here is measured without one)")
     if args.kernels_only:
@@ -221,20 +259,27 @@ def main():
     data = make_sessions(n, clicks)
     total = n * clicks
     runs = [("sequential", lambda c=clicks: run_sequential(mk, data, c))]
-    runs += [(f"pool_k{K}", lambda c=clicks, K=K: run_pool(mk, data, c, K)) for K in ks]
+    stats = {}
+    for K in ks:
+        runs.append((f"pool_k{K}", lambda c=clicks, K=K: run_pool(mk, data, c, K, stats=stats)))
+        if args.prompts != "clicks":
+            runs.append((f"pool_k{K}_{args.prompts}", lambda c=clicks, K=K: run_pool(mk, data, c, K, args.prompts, stats=stats)))
     res, last = {}, {}
     for name, run in runs:
         run(3)                                             # warm-up: the run's own shapes and batch sizes
+        stats.clear()
         secs, last[name] = timed(run)
+        per_round = round(stats["forwards"] / stats["rounds"], 3) if stats else None
         share, forwards = forward_share(model, run)
         copies, nbytes = d2h_traffic(lambda: run(2))       # the profiler pass: two clicks per session
         res[name] = dict(ms_per_click=round(secs / total * 1e3, 3), clicks=total, forwards=forwards, forward_share=share,
                          d2h_copies_per_click=None if copies is None else round(copies / (2 * n), 3),
-                         d2h_bytes_per_click=None if nbytes is None else round(nbytes / (2 * n), 1))
+                         d2h_bytes_per_click=None if nbytes is None else round(nbytes / (2 * n), 1),
+                         forwards_per_round=per_round)
     # bf16: the pool's forward runs other GEMM instantiations than a batch of 2, so the masks are compared, not asserted
     agree = {name: round(float(np.mean([(a == b).mean() for a, b in zip(last[name], last["sequential"])])), 5)
-             for name in last if name != "sequential"}
-    line = {"bench": "sessions", "model": "vitb448", "dtype": "bf16", "sessions": n, "clicks_per_session": clicks,
+             for name in last if name != "sequential" and not name.endswith("_" + args.prompts)}   # (drawn runs: other prompts)
+    line = {"bench": "sessions", "prompts": args.prompts, "model": "vitb448", "dtype": "bf16", "sessions": n, "clicks_per_session": clicks,
             "sizes": SIZES, "results": res, "last_mask_pixel_agreement_with_sequential": agree,
             "pool_over_sequential_ms_per_click": {k: round(v["ms_per_click"] / res["sequential"]["ms_per_click"], 3)
                                                   for k, v in res.items() if k != "sequential"},
