@@ -2891,6 +2891,9 @@ extern "C" int vpu_gemm(const vpu_gemm_desc* d, void* stream) {
             else if (key == 0) VPU_LAUNCH_FL(0, 0, FL_SLAB);
             else if (key == 1) VPU_LAUNCH_FL(0, 1, FL_SLAB);
             else launched = false;
+            // (only the slab forms combine in the launch: transA = 1 / transB = 0, with or without column sums, goes to the
+            // run-time kernel below, whose slices need the reduce launch -- without this C was never written there)
+            if (!launched) { inlaunch = false; cnt_arg = nullptr; }
         }
         if (launched) {
         } else
