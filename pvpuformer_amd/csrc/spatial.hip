@@ -1470,6 +1470,10 @@ __global__ __launch_bounds__(256) void upsample_ac_bwd_kernel(const float* __res
         if (Xlo < 0) Xlo = 0;
         if (Yhi > H - 1) Yhi = H - 1;
         if (Xhi > W - 1) Xhi = W - 1;
+        // a one-row (one-column) input: the step is 0, so is its reciprocal above, and the window would collapse to [0, 1] while
+        // every output row (column) lands on that row -- the whole axis is the window
+        if (h == 1) { Ylo = 0; Yhi = H - 1; }
+        if (w == 1) { Xlo = 0; Xhi = W - 1; }
         const float* g = dout + pl * H * W;
         float acc = 0.f;
         if (Xhi - Xlo < 16) {

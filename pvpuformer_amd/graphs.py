@@ -12,6 +12,8 @@ The cut is lazy: the capture-time hook only notes the range; the graph is closed
 library, so a segment is never empty and kernels that do not go through the library (none today) would land before the
 cut -- a range can be reported later than necessary, never earlier.
 """
+import gc
+
 import torch
 
 from . import _lib, ops
@@ -19,11 +21,44 @@ from . import _lib, ops
 _capture_streams = {}
 
 
+class _CollectorOff:
+    """A capture context with Python's cyclic collector held off while the stream captures.  A collection that starts between
+    two captured launches runs the destructors of whatever dead cycles the process has piled up -- an engine or a training step
+    that owned graphs and their private memory pool among them -- and releasing those mid-capture calls into the runtime
+    (hipFree, hipGraphExecDestroy) from the capturing thread, which ``thread_local`` capture does not allow: the error surfaces
+    in a destructor and the process aborts.  When it strikes depends on the interpreter's allocation counts, that is on
+    everything the process did before.  So: one full collection before the capture begins (torch.cuda.graph leaves that to its
+    caller), none until it has ended.  Nested use (the chain of SegmentedBackward) collects once, at the outermost level."""
+
+    def __init__(self, ctx=None):
+        self.ctx, self.was = ctx, False
+
+    def __enter__(self):
+        self.was = gc.isenabled()
+        if self.was:
+            gc.collect()
+            gc.disable()
+        try:
+            return self.ctx.__enter__() if self.ctx is not None else None
+        except BaseException:
+            if self.was:
+                gc.enable()
+            raise
+
+    def __exit__(self, *exc):
+        try:
+            return self.ctx.__exit__(*exc) if self.ctx is not None else None
+        finally:
+            if self.was:
+                gc.enable()
+
+
 def capture(g, pool=None, device=None):
     """``torch.cuda.graph(g, ...)`` on this package's capture stream of ``device``.  The GEMMs' split-K scratch is kept per
     stream and zero-filled when it is created: created here, before the first capture, the fill is not captured (on torch's
     own capture stream the 128-MB fill became a node of every graph that was the first to need the scratch).
-    ``thread_local`` error mode: RCCL's watchdog thread polls events while a rank captures."""
+    ``thread_local`` error mode: RCCL's watchdog thread polls events while a rank captures.  The cyclic collector is off for
+    the length of the capture (_CollectorOff)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -34,7 +69,7 @@ def capture(g, pool=None, device=None):
             ops.split_k_workspace(dev)
         st.synchronize()
         _capture_streams[dev.index] = st
-    return torch.cuda.graph(g, pool=pool, stream=st, capture_error_mode="thread_local")
+    return _CollectorOff(torch.cuda.graph(g, pool=pool, stream=st, capture_error_mode="thread_local"))
 
 
 class _CutHook:
@@ -96,19 +131,20 @@ class SegmentedBackward:
         # (no reducer: the engine sees no hook -- it queues and launches as in any single-GPU backward -- and nothing is cut)
         eng.grad_ready_hook = None if hook_owner is None else _CutHook(int(getattr(hook_owner, "reserve_cus", 0) or 0), pending).ready
         _lib.call = call
-        open_()
-        try:
-            run()
-        except BaseException:
-            _lib.call, eng.grad_ready_hook = orig_call, orig_hook
+        with _CollectorOff():             # (one collection for the whole chain; also off between two segments)
+            open_()
             try:
-                state["ctx"].__exit__(None, None, None)
-            except Exception:
-                pass
-            eng.abort_pass()          # what the aborted pass queued points at capture-pool buffers nothing has written
-            raise
-        _lib.call, eng.grad_ready_hook = orig_call, orig_hook
-        close_()
+                run()
+            except BaseException:
+                _lib.call, eng.grad_ready_hook = orig_call, orig_hook
+                try:
+                    state["ctx"].__exit__(None, None, None)
+                except Exception:
+                    pass
+                eng.abort_pass()          # what the aborted pass queued points at capture-pool buffers nothing has written
+                raise
+            _lib.call, eng.grad_ready_hook = orig_call, orig_hook
+            close_()
         return self
 
     def replay(self, hook):
