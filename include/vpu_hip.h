@@ -409,6 +409,22 @@ typedef struct vpu_box_row {
 int vpu_box_prompts_batched(const vpu_box_row* rows, int32_t n_rows, const float* points, int32_t n_batch, int32_t S_h,
                             int32_t S_w, float pred_thresh, uint8_t* masks, int32_t* counts, int32_t* roots, int32_t* slots,
                             int32_t* table, int32_t kmax, int32_t* boxes, int32_t* flag, void* stream);
+/* The Crops transform of the predictors (pvpuformer_amd/isegm/inference/transforms/crops.py; isegm/inference/transforms/
+ * crops.py:11-97): the network input cut into a grid of ny x nx overlapping tiles of (ch, cw) pixels, tile t = iy * nx + ix at
+ * (y_offsets[iy], x_offsets[ix]); the offsets are DEVICE int32 arrays of ny and nx entries, arbitrary integers with
+ * 0 <= offset <= H - ch (W - cw).  Each kernel accepts at most VPU_CROPS_MAX_TILES_AXIS tiles per axis.  One launch each for
+ * all tiles; neither allocates nor synchronises.
+ * vpu_crops_gather: in fp32 [C][H][W] -> out fp32 [ny * nx][C][ch][cw], out[t] = in[:, dy:dy+ch, dx:dx+cw].  No alignment is
+ * required; 16-byte loads are taken per tile row where the source address allows, 16-byte stores when cw % 4 == 0 and out is
+ * 16-byte aligned.  A tile whose offsets leave the image is not written.
+ * vpu_crops_blend: probs fp32 [ny * nx][ch][cw] -> out fp32 [H][W]: per pixel the values of the covering tiles added to 0 in
+ * tile order (iy ascending, ix ascending inside), divided (correctly rounded) by their number -- the bits of the reference's
+ * zeros / += / torch.div.  Every pixel of out is written, none is read; a pixel that no tile covers gets 0 / 0. */
+#define VPU_CROPS_MAX_TILES_AXIS 64
+int vpu_crops_gather(const float* in, float* out, const int32_t* y_offsets, const int32_t* x_offsets, int32_t ny, int32_t nx,
+                     int32_t C, int32_t H, int32_t W, int32_t ch, int32_t cw, void* stream);
+int vpu_crops_blend(const float* probs, float* out, const int32_t* y_offsets, const int32_t* x_offsets, int32_t ny, int32_t nx,
+                    int32_t H, int32_t W, int32_t ch, int32_t cw, void* stream);
 /* 8-connected components of B masks [B][H][W]: roots[i] = smallest linear index (within the whole [B][H][W] array) of the
  * component of non-zero pixel i, -1 on zero pixels.  Sorted by root, the components are in the raster order of their first
  * pixel -- the label order of the reference's skimage.measure.label(connectivity=2) in max_connected_regions

@@ -124,6 +124,8 @@ SIGNATURES = {
     "vpu_session_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vpu_crops_blend": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_disk_maps": [_P, _P, _P, _I, _I, _I, _I, _F, _P],
     "vpu_patch_im2col": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vpu_patch_im2col_prenorm": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

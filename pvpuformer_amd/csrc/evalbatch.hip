@@ -479,7 +479,130 @@ __global__ __launch_bounds__(256) void session_paste_quad_kernel(const vpu_sessi
     session_reduce(d, a);
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (6) Crops (pvpuformer_amd/isegm/inference/transforms/crops.py): the network input cut into a grid of overlapping tiles
+//     of the trained size, and the tiles' probabilities averaged back.  Both are plain streams, one launch for all tiles.
+//
+//     gather: tile t = iy * nx + ix (blockIdx.y) = in[:, dy:dy+ch, dx:dx+cw].  4 pixels of a tile row per thread.  The offsets
+//     are arbitrary integers and W need not be a multiple of 4, so a source quad is 16-byte aligned only where
+//     (c * H + dy + r) * W + dx is a multiple of 4: that holds or fails for a whole tile row at once (the quads of a row
+//     start 4 floats apart), and a row takes the 16-byte loads when it holds, scalar loads otherwise.  The destination is
+//     dense: 16-byte stores whenever cw % 4 == 0 (vec_out).  A tile whose offsets leave the image is not written.
+__global__ __launch_bounds__(256) void crops_gather_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                           const int* __restrict__ y_off, const int* __restrict__ x_off, int C,
+                                                           int H, int W, int ch, int cw, int nx, int vec_in, int vec_out) {
+    const int t = blockIdx.y, dy = y_off[t / nx], dx = x_off[t % nx];
+    if (dy < 0 || dx < 0 || dy > H - ch || dx > W - cw) return;
+    const int quads = (cw + 3) / 4;
+    const int64_t total = (int64_t)C * ch * quads;
+    float* dst = out + (int64_t)t * C * ch * cw;
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += (int64_t)gridDim.x * 256) {
+        const int j = (int)(q % quads) * 4;
+        const int r = (int)((q / quads) % ch);
+        const int c = (int)(q / ((int64_t)quads * ch));
+        const int64_t s = ((int64_t)c * H + dy + r) * W + dx + j;
+        const int64_t o = ((int64_t)c * ch + r) * cw + j;
+        const int nv = cw - j < 4 ? cw - j : 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (nv == 4 && vec_in && (s & 3) == 0) {
+            const float4 f = *reinterpret_cast<const float4*>(in + s);
+            v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (u < nv) v[u] = in[s + u];
+        }
+        if (nv == 4 && vec_out) {
+            *reinterpret_cast<float4*>(dst + o) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (u < nv) dst[o + u] = v[u];
+        }
+    }
+}
+
+//     blend: every output pixel is computed by the lane that owns it -- the covering tiles' values added in tile order (iy
+//     ascending, ix ascending inside) to 0, then ONE correctly rounded division by their number: the bits of
+//     ``zeros; canvas[tile] += probs[t] for t in order; canvas / counts``.  No atomics, and nothing is read from out.
+//     A pixel no tile covers is 0 / 0.
+__device__ __forceinline__ float crops_blend_pixel(const float* __restrict__ probs, const int* __restrict__ y_off,
+                                                   const int* __restrict__ x_off, int ny, int nx, int ch, int cw, int r, int c) {
+    const int64_t plane = (int64_t)ch * cw;
+    float acc = 0.f;
+    int cover = 0;
+    for (int iy = 0; iy < ny; ++iy) {
+        const int y = r - y_off[iy];
+        if (y < 0 || y >= ch) continue;
+        for (int ix = 0; ix < nx; ++ix) {
+            const int x = c - x_off[ix];
+            if (x < 0 || x >= cw) continue;
+            acc += probs[((int64_t)iy * nx + ix) * plane + (int64_t)y * cw + x];
+            ++cover;
+        }
+    }
+    return acc / (float)cover;
+}
+
+// 4 consecutive pixels of the flat [H * W] map per thread (they may lie in two rows when W % 4 != 0): one 16-byte store
+__global__ __launch_bounds__(256) void crops_blend_kernel(const float* __restrict__ probs, float* __restrict__ out,
+                                                          const int* __restrict__ y_off, const int* __restrict__ x_off, int ny,
+                                                          int nx, int H, int W, int ch, int cw, int vec_out) {
+    const int64_t HW = (int64_t)H * W, quads = (HW + 3) >> 2;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < quads; k += (int64_t)gridDim.x * 256) {
+        const int64_t i0 = k << 2;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i0 + u < HW) {
+                const int r = (int)((i0 + u) / W), c = (int)((i0 + u) - (int64_t)r * W);
+                v[u] = crops_blend_pixel(probs, y_off, x_off, ny, nx, ch, cw, r, c);
+            }
+        }
+        if (vec_out && i0 + 3 < HW) {
+            *reinterpret_cast<float4*>(out + i0) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u < HW) out[i0 + u] = v[u];
+        }
+    }
+}
+
 }  // namespace
+
+static bool crops_sizes_ok(int32_t ny, int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw) {
+    return ny >= 1 && nx >= 1 && ny <= VPU_CROPS_MAX_TILES_AXIS && nx <= VPU_CROPS_MAX_TILES_AXIS && ch >= 1 && cw >= 1 &&
+           ch <= H && cw <= W;
+}
+
+extern "C" int vpu_crops_gather(const float* in, float* out, const int32_t* y_offsets, const int32_t* x_offsets, int32_t ny,
+                                int32_t nx, int32_t C, int32_t H, int32_t W, int32_t ch, int32_t cw, void* stream) {
+    vpu_clear_stale_error();
+    if (!in || !out || !y_offsets || !x_offsets || C < 1 || !crops_sizes_ok(ny, nx, H, W, ch, cw)) {
+        vpu_set_error("crops_gather: null pointer or sizes (1 <= ny, nx <= VPU_CROPS_MAX_TILES_AXIS, 1 <= ch <= H, 1 <= cw <= W)");
+        return VPU_ERR_ARG;
+    }
+    const int vec_in = reinterpret_cast<uintptr_t>(in) % 16 == 0;
+    const int vec_out = cw % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const int nb = vpu_grid_for((long long)C * ch * ((cw + 3) / 4), 256, 256);
+    crops_gather_kernel<<<dim3((unsigned)nb, (unsigned)(ny * nx)), 256, 0, ST>>>(in, out, y_offsets, x_offsets, C, H, W, ch, cw,
+                                                                                nx, vec_in, vec_out);
+    return vpu_check_launch("vpu_crops_gather");
+}
+
+extern "C" int vpu_crops_blend(const float* probs, float* out, const int32_t* y_offsets, const int32_t* x_offsets, int32_t ny,
+                               int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw, void* stream) {
+    vpu_clear_stale_error();
+    if (!probs || !out || !y_offsets || !x_offsets || !crops_sizes_ok(ny, nx, H, W, ch, cw)) {
+        vpu_set_error("crops_blend: null pointer or sizes (1 <= ny, nx <= VPU_CROPS_MAX_TILES_AXIS, 1 <= ch <= H, 1 <= cw <= W)");
+        return VPU_ERR_ARG;
+    }
+    const int vec_out = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const int nb = vpu_grid_for(((long long)H * W + 3) / 4, 256, 4096);
+    crops_blend_kernel<<<(unsigned)nb, 256, 0, ST>>>(probs, out, y_offsets, x_offsets, ny, nx, H, W, ch, cw, vec_out);
+    return vpu_check_launch("vpu_crops_blend");
+}
 
 extern "C" int vpu_session_paste_batched(const vpu_session_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w,
                                          float pred_thr, float box_thr, int32_t max_hw, int32_t form, void* stream) {

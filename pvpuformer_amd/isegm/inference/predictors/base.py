@@ -1,17 +1,19 @@
 """NoBRS predictor, API-compatible with the hot calls of isegm/inference/predictors/base.py:10-223:
 ``set_input_image / get_prediction / get_vqu_prediction / get_points_nd / apply_transforms / get_states / set_states``.
-Transform pipeline as in the reference (base.py:42-48): [ZoomIn] [LimitLongestSide] [SigmoidForPred] [AddHorizontalFlip],
-inverted in reverse order (so the flip average is taken on logits, before the sigmoid)."""
+Transform pipeline as in the reference (base.py:42-48): [ZoomIn] [LimitLongestSide] [Crops] [SigmoidForPred]
+[AddHorizontalFlip], inverted in reverse order (so the flip average is taken on logits, before the sigmoid, and ``Crops``
+blends probabilities).  With ``Crops`` the network batch is ``tiles`` rows, ``2 * tiles`` with the flip."""
 import numpy as np
 import torch
 
 from ...engine.prompt_sim import get_next_promts
-from ..transforms import AddHorizontalFlip, LimitLongestSide, SigmoidForPred, crop_resize, resize_align_corners
+from ..transforms import AddHorizontalFlip, Crops, LimitLongestSide, SigmoidForPred, crop_resize, resize_align_corners
 
 
 class BasePredictor:
     def __init__(self, model, device, net_clicks_limit=None, with_flip=False, with_sigmoid=True, zoom_in=None,
-                 max_size=None, cascade_step=0, cascade_adaptive=False, cascade_clicks=1, **kwargs):
+                 max_size=None, cascade_step=0, cascade_adaptive=False, cascade_clicks=1, crops=None, net_rows_limit=None,
+                 **kwargs):
         # base.py:109-125 -- the cascade re-prediction of the first clicks (cascade_step >= 2) and the per-click model list
         # (`model` given as a (net, click_models) tuple) are side branches that are not mirrored, and refused here rather than
         # silently ignored.  cascade_step = 1 is what the shipped script passes with its default
@@ -32,6 +34,15 @@ class BasePredictor:
         self.transforms = [zoom_in] if zoom_in is not None else []
         if max_size is not None:
             self.transforms.append(LimitLongestSide(max_size=max_size))
+        if crops is not None:
+            if not isinstance(crops, Crops):
+                raise TypeError("BasePredictor(crops=...): a transforms.Crops instance (get_predictor builds one from crops_params)")
+            self.transforms.append(crops)
+        self.crops = crops
+        # with more rows than this (tiles, and their flip copies) the network runs over consecutive row chunks (_run_net)
+        if net_rows_limit is not None and int(net_rows_limit) < 1:
+            raise ValueError("BasePredictor(net_rows_limit=...): at least 1, or None for one forward over all rows")
+        self.net_rows_limit = None if net_rows_limit is None else int(net_rows_limit)
         if with_sigmoid:
             self.transforms.append(SigmoidForPred())
         if with_flip:
@@ -81,6 +92,23 @@ class BasePredictor:
         image_nd, clicks_lists, _ = self.apply_transforms(image_nd, [clicks_list])
         return image_nd, clicks_lists, prev_mask
 
+    def _run_net(self, image_nd, points_nd, prompts=None, as_prompt_type=None):
+        """The network's logits of every row; above ``net_rows_limit`` rows, computed in consecutive chunks of at most that many
+        and concatenated (rows are independent of one another)."""
+        def call(image, points, given):
+            if given is None:
+                return self.net(image, points)['instances']
+            return self.net(image, points, given, as_prompt_type)['instances']
+
+        n, limit = image_nd.shape[0], self.net_rows_limit
+        if limit is None or n <= limit:
+            return call(image_nd, points_nd, prompts)
+        chunks = []
+        for i in range(0, n, limit):
+            given = None if prompts is None else tuple(None if p is None else p[i:i + limit] for p in prompts)
+            chunks.append(call(image_nd[i:i + limit], points_nd[i:i + limit], given))
+        return torch.cat(chunks, dim=0)
+
     def _finish(self, logits, image_nd):
         pred = logits
         if tuple(pred.shape[2:]) != tuple(image_nd.shape[2:]):   # base.py:93-94 (a no-op at the model's own size)
@@ -92,7 +120,7 @@ class BasePredictor:
     @torch.no_grad()
     def get_prediction(self, clicker, prev_mask=None):
         image_nd, clicks_lists, _ = self._net_input(clicker, prev_mask)
-        logits = self.net(image_nd, self.get_points_nd(clicks_lists).float())['instances']   # base.py:102-104
+        logits = self._run_net(image_nd, self.get_points_nd(clicks_lists).float())            # base.py:102-104
         pred = self._finish(logits, image_nd)
         if self.zoom_in is not None and self.zoom_in.check_possible_recalculation():
             return self.get_prediction(clicker)
@@ -109,9 +137,14 @@ class BasePredictor:
             raise NotImplementedError("get_vqu_prediction(as_multi_prompts=False): the get_next_promts_inference branch of "
                                       "base.py:154-164 is not mirrored (the shipped evaluation passes True, vpu_evaluation.py:43)")
         image_nd, clicks_lists, prev = self._net_input(clicker, prev_mask)
+        tiled = self.crops is not None and self.crops.num_tiles > 1
+        if tiled and as_prompt_type != 0:
+            # the box and the scribble are derived from the un-tiled masks: one row per flip copy, not one per tile
+            raise ValueError(f"get_vqu_prediction(as_prompt_type={as_prompt_type}): only click prompts (0) run on a Crops input "
+                             f"of several tiles ({self.crops.num_tiles} here)")
         points_nd = self.get_points_nd(clicks_lists).float()
         boxes = scribbles = None
-        if as_prompt_type != 0 or self.always_simulate_prompts:
+        if as_prompt_type != 0 or (self.always_simulate_prompts and not tiled):
             # the reference derives the box prompt on EVERY click (base.py:176), also for click prompts, where the network
             # never reads it: here it is simulated only when it is consumed (~3 ms of a 7.5-ms click otherwise) -- by the
             # network (as_prompt_type != 0) or by a caller that reads ``prompts[1]``: ``always_simulate_prompts=True`` (a
@@ -129,7 +162,7 @@ class BasePredictor:
             else:
                 _, boxes = get_next_promts(prev, gt, points_nd, None, as_allmask=False, jitter_box=False)
         prompts = (points_nd, boxes, scribbles)
-        logits = self.net(image_nd, points_nd, prompts, as_prompt_type)['instances']
+        logits = self._run_net(image_nd, points_nd, prompts, as_prompt_type)
         pred = self._finish(logits, image_nd)
         if self.zoom_in is not None and self.zoom_in.check_possible_recalculation():
             return self.get_prediction(clicker), prompts

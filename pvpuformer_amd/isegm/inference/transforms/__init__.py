@@ -2,6 +2,7 @@
 ``transform / inv_transform / reset / get_state / set_state`` and the ``image_changed`` flag."""
 from . import _device
 from .base import BaseTransform, SigmoidForPred
+from .crops import Crops, get_offsets
 from .flip import AddHorizontalFlip
 from .limit_longest_side import LimitLongestSide
 from .roi import Roi

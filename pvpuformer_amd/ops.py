@@ -496,6 +496,42 @@ def box_prompts_batched(rows, n_rows, points, n_batch, S_h, S_w, pred_thresh, fl
     return boxes
 
 
+CROPS_MAX_TILES_AXIS = 64   # VPU_CROPS_MAX_TILES_AXIS (include/vpu_hip.h)
+
+
+def _crops_check(name, y_off, x_off, ny, nx):
+    if not 1 <= ny <= CROPS_MAX_TILES_AXIS or not 1 <= nx <= CROPS_MAX_TILES_AXIS:
+        raise ValueError(f"{name}: {ny} x {nx} tiles; the kernel accepts 1 to {CROPS_MAX_TILES_AXIS} per axis")
+    for off, n in ((y_off, ny), (x_off, nx)):
+        assert off.is_cuda and off.dtype == torch.int32 and off.is_contiguous() and off.numel() == n
+
+
+def crops_gather(image, y_off, x_off, ch, cw):
+    """image fp32 [C, H, W] -> fp32 [ny * nx, C, ch, cw]: tile iy * nx + ix = image[:, dy:dy+ch, dx:dx+cw] with the offsets
+    taken from the device int32 arrays ``y_off`` / ``x_off`` (0 <= offset <= H - ch / W - cw: the caller's to keep)."""
+    C_, H, W = image.shape
+    ny, nx = int(y_off.numel()), int(x_off.numel())
+    _crops_check("crops_gather", y_off, x_off, ny, nx)
+    assert image.dtype == torch.float32 and image.is_contiguous()
+    out = torch.empty(ny * nx, C_, ch, cw, device=image.device, dtype=torch.float32)
+    _lib.call("vpu_crops_gather", ptr(image), ptr(out), ptr(y_off), ptr(x_off), ny, nx, C_, H, W, ch, cw, _stream())
+    return out
+
+
+def crops_blend(probs, y_off, x_off, H, W, out=None):
+    """probs fp32 [ny * nx, ch, cw] -> fp32 [H, W]: the tiles added in tile order where they cover a pixel, divided by their
+    number (vpu_crops_blend); every pixel of ``out`` is written."""
+    T, ch, cw = probs.shape
+    ny, nx = int(y_off.numel()), int(x_off.numel())
+    _crops_check("crops_blend", y_off, x_off, ny, nx)
+    assert probs.dtype == torch.float32 and probs.is_contiguous() and T == ny * nx
+    if out is None:
+        out = torch.empty(H, W, device=probs.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (H, W)
+    _lib.call("vpu_crops_blend", ptr(probs), ptr(out), ptr(y_off), ptr(x_off), ny, nx, H, W, ch, cw, _stream())
+    return out
+
+
 def disk_maps(points, boxes, out, B, n, H, W, radius):
     _lib.call("vpu_disk_maps", ptr(points), ptr(boxes), ptr(out), B, n, H, W, float(radius), _stream())
 
