@@ -385,6 +385,30 @@ typedef struct vpu_session_obj {
  * Neither allocates nor synchronises. */
 int vpu_session_paste_batched(const vpu_session_obj* objs, int32_t n, const float* probs, int32_t S_h, int32_t S_w,
                               float pred_thr, float box_thr, int32_t max_hw, int32_t form, void* stream);
+/* Multi-object annotation over the sessions (pvpuformer_amd/isegm/inference/annotation.py).  The object being edited is
+ * cur = max(total, add) of two fp32 [H][W] maps, the parts finished so far and the session's prediction; its mask is
+ * cur > thr (strict).  One launch covers n annotations of different image sizes:
+ *   add, total: fp32 [H][W], 16-byte aligned, or NULL for a map of zeros (a NULL total is never written);
+ *   labels: uint16 [H][W], 8-byte aligned, or NULL; bits = ceil(H * W / 64) little-endian 64-bit words (8-byte aligned);
+ *   rec = int32 [8]; label = the 16-bit value written; mode: bit 0 writes total = cur, bit 1 writes labels = label where the
+ *   mask is set (and nowhere else). */
+typedef struct vpu_annot_obj {
+    const float* add;
+    float* total;
+    uint16_t* labels;
+    uint64_t* bits;
+    int32_t* rec;
+    int32_t H, W, label, mode;
+} vpu_annot_obj;
+/* Always written: bits, the mask in vpu_session_paste_batched's bit order (bits at or beyond H * W are zero, every word is
+ * stored once by the lanes that own it), and rec = {area, overwritten, rmin, rmax, cmin, cmax, 0, 0}: the mask's pixel count,
+ * how many of them held a label other than 0 and ``label`` before the call (0 without labels), and the mask's inclusive box
+ * ({H, -1, W, -1} when it is empty).  Four pixels per lane: 16-byte loads of both maps, the four labels in one 8-byte access.
+ * max_hw >= every H * W.  Neither allocates nor synchronises. */
+int vpu_annot_compose_batched(const vpu_annot_obj* objs, int32_t n, float thr, int32_t max_hw, void* stream);
+/* One annotation: out fp32 [H][W] (16-byte aligned) = labels == label ? 1 : 0, every pixel written; those pixels of labels
+ * (uint16 [H][W], 8-byte aligned) become 0; rec = {area, 0, rmin, rmax, cmin, cmax, 0, 0} of them.  1 <= label <= 65535. */
+int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int32_t H, int32_t W, int32_t label, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

@@ -73,6 +73,12 @@ class SessionObj(C.Structure):
                 ("c1", C.c_int32), ("src", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AnnotObj(C.Structure):
+    """vpu_annot_obj (include/vpu_hip.h): one annotation of vpu_annot_compose_batched."""
+    _fields_ = [("add", C.c_void_p), ("total", C.c_void_p), ("labels", C.c_void_p), ("bits", C.c_void_p), ("rec", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("label", C.c_int32), ("mode", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -122,6 +128,8 @@ SIGNATURES = {
     "vpu_roi_resize_batched": [_P, _I, _P, _I, _I, _I, _I, _P],
     "vpu_roi_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _P],
     "vpu_session_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _I, _P],
+    "vpu_annot_compose_batched": [_P, _I, _F, _I, _P],
+    "vpu_label_extract": [_P, _P, _P, _I, _I, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -569,6 +569,189 @@ __global__ __launch_bounds__(256) void crops_blend_kernel(const float* __restric
     }
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (7) multi-object annotation (isegm/inference/annotation.py): the object being edited is cur = max(total, add) of two fp32
+//     maps (the finished parts and the session's prediction), its mask cur > thr.  One launch composes n annotations of
+//     different sizes: the packed mask in (5)'s bit order, rec = {area, overwritten, rmin, rmax, cmin, cmax, 0, 0}, and by
+//     mode total = cur (bit 0) and labels = label where the mask is set (bit 1).  The quad form of (5): four pixels per lane,
+//     16-byte loads of both maps, the four labels of a quad in one 8-byte load and, when the mask touches them, one store;
+//     the quad is owned by its lane, so the pixels whose bit is clear are written back as they were read.
+struct AnnotAcc {
+    int area = 0, over = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
+};
+
+__device__ __forceinline__ void annot_rec_init(int* s, int H, int W) {
+    s[0] = 0; s[1] = 0; s[2] = H; s[3] = -1; s[4] = W; s[5] = -1; s[6] = 0; s[7] = 0;
+}
+
+__global__ void annot_init_kernel(const vpu_annot_obj* __restrict__ objs, int n) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    annot_rec_init(objs[b].rec, objs[b].H, objs[b].W);
+}
+
+__global__ void annot_init_one_kernel(int* rec, int H, int W) { annot_rec_init(rec, H, W); }
+
+// session_reduce's block reduction; the box is that of the mask, so it is merged whenever the block has mask pixels
+__device__ __forceinline__ void annot_reduce(int* s, AnnotAcc a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.area += __shfl_xor(a.area, o, 64); a.over += __shfl_xor(a.over, o, 64);
+        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
+        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
+    }
+    __shared__ int red[4][6];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave][0] = a.area; red[wave][1] = a.over;
+        red[wave][2] = a.r0; red[wave][3] = a.r1; red[wave][4] = a.c0; red[wave][5] = a.c1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            red[0][0] += red[k][0]; red[0][1] += red[k][1];
+            red[0][2] = min(red[0][2], red[k][2]); red[0][3] = max(red[0][3], red[k][3]);
+            red[0][4] = min(red[0][4], red[k][4]); red[0][5] = max(red[0][5], red[k][5]);
+        }
+        if (red[0][1]) atomicAdd(s + 1, red[0][1]);
+        if (red[0][0]) {
+            atomicAdd(s + 0, red[0][0]);
+            atomicMin(s + 2, red[0][2]); atomicMax(s + 3, red[0][3]); atomicMin(s + 4, red[0][4]); atomicMax(s + 5, red[0][5]);
+        }
+    }
+}
+
+// the mask pixel (r, c) u places after the quad's first pixel (r0, c0): a quad may span several rows when W < 4
+__device__ __forceinline__ void annot_count(AnnotAcc& a, int r, int c, int W) {
+    while (c >= W) { c -= W; ++r; }
+    ++a.area;
+    a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
+}
+
+__global__ __launch_bounds__(256) void annot_compose_kernel(const vpu_annot_obj* __restrict__ objs, float thr) {
+    const vpu_annot_obj& d = objs[blockIdx.y];
+    if (d.H < 1 || d.W < 1) return;
+    const int64_t HW = (int64_t)d.H * d.W, words = (HW + 63) >> 6, turns = (HW + 255) >> 8;
+    const int lane = threadIdx.x & 63;
+    const bool put_total = (d.mode & 1) && d.total, put_labels = (d.mode & 2) && d.labels;
+    const unsigned label = (unsigned)d.label & 0xffffu;
+    AnnotAcc a;
+    for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < turns; k += (int64_t)gridDim.x * 4) {
+        const int64_t i0 = (k << 8) + 4 * lane;
+        const bool full = i0 + 3 < HW;
+        float t[4] = {0.f, 0.f, 0.f, 0.f}, ad[4] = {0.f, 0.f, 0.f, 0.f};
+        unsigned lb[4] = {0u, 0u, 0u, 0u};
+        if (full) {
+            if (d.total) {
+                const float4 f = *reinterpret_cast<const float4*>(d.total + i0);
+                t[0] = f.x; t[1] = f.y; t[2] = f.z; t[3] = f.w;
+            }
+            if (d.add) {
+                const float4 f = *reinterpret_cast<const float4*>(d.add + i0);
+                ad[0] = f.x; ad[1] = f.y; ad[2] = f.z; ad[3] = f.w;
+            }
+            if (d.labels) {
+                const uint2 q = *reinterpret_cast<const uint2*>(d.labels + i0);
+                lb[0] = q.x & 0xffffu; lb[1] = q.x >> 16; lb[2] = q.y & 0xffffu; lb[3] = q.y >> 16;
+            }
+        } else {                                                      // the quad that holds the last H * W % 4 pixels, or none
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + u < HW) {
+                    if (d.total) t[u] = d.total[i0 + u];
+                    if (d.add) ad[u] = d.add[i0 + u];
+                    if (d.labels) lb[u] = d.labels[i0 + u];
+                }
+            }
+        }
+        unsigned nib = 0;
+        if (i0 < HW) {
+            const int r0 = (int)(i0 / d.W), c0 = (int)(i0 - (int64_t)r0 * d.W);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + u < HW) {
+                    t[u] = fmaxf(t[u], ad[u]);
+                    if (t[u] > thr) {
+                        nib |= 1u << u;
+                        annot_count(a, r0, c0 + u, d.W);
+                        if (lb[u] != 0u && lb[u] != label) ++a.over;
+                        lb[u] = label;
+                    }
+                }
+            }
+        }
+        if (put_total) {
+            if (full) {
+                *reinterpret_cast<float4*>(d.total + i0) = make_float4(t[0], t[1], t[2], t[3]);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (i0 + u < HW) d.total[i0 + u] = t[u];
+            }
+        }
+        if (put_labels && nib) {
+            if (full) {
+                *reinterpret_cast<uint2*>(d.labels + i0) = make_uint2(lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16));
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (nib & (1u << u)) d.labels[i0 + u] = (uint16_t)lb[u];
+            }
+        }
+        unsigned long long word = (unsigned long long)nib << (4 * (lane & 15));
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
+        const int64_t at = (k << 2) + (lane >> 4);
+        if ((lane & 15) == 0 && at < words) d.bits[at] = word;
+    }
+    annot_reduce(d.rec, a);
+}
+
+// out = (labels == label) ? 1 : 0, and those label pixels become 0: the mask a committed object is reopened with
+__global__ __launch_bounds__(256) void label_extract_kernel(uint16_t* __restrict__ labels, float* __restrict__ out,
+                                                            int* __restrict__ rec, int H, int W, unsigned label) {
+    const int64_t HW = (int64_t)H * W, quads = (HW + 3) >> 2;
+    AnnotAcc a;
+    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < quads; k += (int64_t)gridDim.x * 256) {
+        const int64_t i0 = k << 2;
+        const bool full = i0 + 3 < HW;
+        unsigned lb[4] = {0u, 0u, 0u, 0u};
+        if (full) {
+            const uint2 q = *reinterpret_cast<const uint2*>(labels + i0);
+            lb[0] = q.x & 0xffffu; lb[1] = q.x >> 16; lb[2] = q.y & 0xffffu; lb[3] = q.y >> 16;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i0 + u < HW) lb[u] = labels[i0 + u];
+        }
+        const int r0 = (int)(i0 / W), c0 = (int)(i0 - (int64_t)r0 * W);
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        unsigned nib = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i0 + u < HW && lb[u] == label) {
+                nib |= 1u << u;
+                v[u] = 1.f;
+                lb[u] = 0u;
+                annot_count(a, r0, c0 + u, W);
+            }
+        }
+        if (full) {
+            *reinterpret_cast<float4*>(out + i0) = make_float4(v[0], v[1], v[2], v[3]);
+            if (nib) *reinterpret_cast<uint2*>(labels + i0) = make_uint2(lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16));
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + u < HW) {
+                    out[i0 + u] = v[u];
+                    if (nib & (1u << u)) labels[i0 + u] = 0;
+                }
+            }
+        }
+    }
+    annot_reduce(rec, a);
+}
+
 }  // namespace
 
 static bool crops_sizes_ok(int32_t ny, int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw) {
@@ -692,4 +875,32 @@ extern "C" int vpu_click_keys_batched(const vpu_eval_obj* objs, int32_t n, uint8
     const int na = vpu_grid_for(max_hw, 2048, 128);
     click_argmax_kernel<<<dim3((unsigned)na, (unsigned)(2 * n)), 256, 0, ST>>>(objs, dist, Hm, Wm);
     return vpu_check_launch("vpu_click_keys_batched (arg-max)");
+}
+
+extern "C" int vpu_annot_compose_batched(const vpu_annot_obj* objs, int32_t n, float thr, int32_t max_hw, void* stream) {
+    vpu_clear_stale_error();
+    if (!objs || n < 1 || n > 65535 || max_hw < 1 || !(thr == thr)) {
+        vpu_set_error("annot_compose_batched: null descriptors, sizes (1 <= n <= 65535, max_hw >= 1) or a NaN threshold");
+        return VPU_ERR_ARG;
+    }
+    annot_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    const int nb = vpu_grid_for(max_hw, 1024, 128);
+    annot_compose_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, thr);
+    return vpu_check_launch("vpu_annot_compose_batched");
+}
+
+extern "C" int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int32_t H, int32_t W, int32_t label, void* stream) {
+    vpu_clear_stale_error();
+    if (!labels || !out || !rec || H < 1 || W < 1 || (int64_t)H * W > 0x7fffffff || label < 1 || label > 65535) {
+        vpu_set_error("label_extract: null pointer, sizes (H, W >= 1, H * W < 2^31) or label (1 <= label <= 65535)");
+        return VPU_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(labels) % 8 || reinterpret_cast<uintptr_t>(out) % 16 || reinterpret_cast<uintptr_t>(rec) % 4) {
+        vpu_set_error("label_extract: labels not 8-byte, out not 16-byte or rec not 4-byte aligned");
+        return VPU_ERR_ALIGN;
+    }
+    annot_init_one_kernel<<<1, 1, 0, ST>>>(rec, H, W);
+    const int nb = vpu_grid_for(((long long)H * W + 3) / 4, 256, 1024);
+    label_extract_kernel<<<(unsigned)nb, 256, 0, ST>>>(labels, out, rec, H, W, (unsigned)label);
+    return vpu_check_launch("vpu_label_extract");
 }

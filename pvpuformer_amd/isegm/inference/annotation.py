@@ -1,0 +1,390 @@
+"""Multi-object annotation over ``SessionPool``: several objects per image, objects built from parts, initial masks, undo
+and reopening, with every map on the device.
+
+A ``SessionPool`` session is one object: one probability canvas, one bit-packed mask per click.  ``AnnotationPool`` keeps,
+per image, a 16-bit label map of the committed objects and the object being edited -- its click list, the parts finished
+so far (``parts``), an optional initial mask and an undo stack -- and drives one pool session per image through the pool's
+public methods only (``open / close / predict / probs / get_states / set_states``).  The rules:
+
+  R1  current = max(parts, additive), the mask is current > prob_thresh (strict); additive is the session's previous
+      prediction, zeros while the object has no clicks.
+  R2  the preview label map is ``labels`` with object_count + 1 under the current mask; ``labels`` is not modified.
+  R3  a click is appended and predicted through the pool; an initial mask is that session's ``prev_masks`` entry on every
+      click, and the first click of such an object is predicted twice.
+  R4  partial finish: parts = current, the click list emptied, the session reset, the initial mask cleared.
+  R5  finish: labels = object_count + 1 under the current mask (earlier objects are overwritten there), the count goes up,
+      the record is appended, the object starts anew.
+  R6  undo restores the object as it was before its last click or partial finish (a stack of at most ``max_undo``).
+  R7  an initial mask stands in for ``parts`` until a partial finish or finish clears it.
+  R8  reopen removes a committed label from ``labels`` and makes its pixels the initial mask.
+
+All of this is max, a strict compare and integer writes, done by ``vpu_annot_compose_batched`` / ``vpu_label_extract``
+(csrc/evalbatch.hip, section 7): what crosses to the host is the packed mask (``H * W / 8`` bytes) or the 32-byte record,
+never an fp32 map.  On a CPU predictor the numpy stand-ins ``host_annot_compose`` / ``host_label_extract`` run instead
+(``HostAnnotOps``); ``pool.ops`` may be replaced by them on a device pool, which is how the GPU tests build their twin."""
+import numpy as np
+import torch
+
+from .clicker import Click, Clicker
+from .sessions import SessionPool, n_words, pack_mask, unpack_mask
+
+MAX_LABEL = 65535
+_REC = 4             # int64 per record (int32 [8]: area, overwritten, rmin, rmax, cmin, cmax, 0, 0)
+
+
+# ------------------------------------------------------------------------------------------------------ host stand-ins
+def _record(mask, overwritten):
+    H, W = mask.shape
+    on = np.argwhere(mask)
+    box = [int(on[:, 0].min()), int(on[:, 0].max()), int(on[:, 1].min()), int(on[:, 1].max())] if len(on) else [H, -1, W, -1]
+    return np.array([len(on), overwritten] + box + [0, 0], dtype=np.int32)
+
+
+def host_annot_compose(add, total, labels, H, W, label, mode, thr):
+    """Stand-in of vpu_annot_compose_batched for one annotation.  ``add`` / ``total``: fp32 [H, W] or None (zeros), ``labels``:
+    uint16 [H, W] or None; ``total`` and ``labels`` are written in place as ``mode`` says -> (packed mask uint64, record
+    int32 [8])."""
+    zeros = np.zeros((H, W), dtype=np.float32)
+    cur = np.maximum(zeros if total is None else total, zeros if add is None else add)
+    mask = cur > np.float32(thr)
+    over = 0 if labels is None else int((mask & (labels != 0) & (labels != np.uint16(label))).sum())
+    if mode & 1 and total is not None:
+        total[...] = cur
+    if mode & 2 and labels is not None:
+        labels[mask] = np.uint16(label)
+    return pack_mask(mask), _record(mask, over)
+
+
+def host_label_extract(labels, label):
+    """Stand-in of vpu_label_extract: ``labels`` uint16 [H, W], its ``label`` pixels set to 0 in place -> (fp32 [H, W] of
+    1 / 0, record int32 [8])."""
+    mask = labels == np.uint16(label)
+    labels[mask] = 0
+    return mask.astype(np.float32), _record(mask, 0)
+
+
+# ------------------------------------------------------------------------------------------------------ the two kernels
+class _Item:
+    """One row of a compose call; ``add`` / ``total`` fp32 [H, W] tensors or None, ``labels`` int16 [H, W] tensor or None."""
+
+    def __init__(self, H, W, add=None, total=None, labels=None, label=0, mode=0):
+        self.H, self.W, self.add, self.total, self.labels, self.label, self.mode = H, W, add, total, labels, int(label), int(mode)
+
+
+def _decode(got, items, at, masks):
+    out = []
+    for i, it in enumerate(items):
+        rec = got[_REC * i:_REC * (i + 1)].view(np.int32)
+        out.append((rec, unpack_mask(got[at[i]:at[i] + n_words(it.H * it.W)], it.H, it.W) if masks else None))
+    return out
+
+
+class DeviceAnnotOps:
+    """The HIP kernels: the descriptors of a call go up in one copy, its records and packed masks come back in one."""
+
+    def __init__(self, device):
+        from pvpuformer_amd import _lib, ops
+        self._lib, self._ops, self.device = _lib, ops, torch.device(device)
+
+    def compose(self, items, thr, read):
+        """``read``: "masks" -> [(record, mask bool [H, W])], "records" -> [(record, None)] (one read-back each), None ->
+        nothing is read back and nothing waited for."""
+        n, at, size = len(items), [], _REC * len(items)
+        for it in items:
+            at.append(size)
+            size += n_words(it.H * it.W)
+        out = torch.empty(size, device=self.device, dtype=torch.int64)
+        assert out.data_ptr() % 8 == 0
+        rows = []
+        for i, it in enumerate(items):
+            assert it.H >= 1 and it.W >= 1 and it.H * it.W < 2 ** 31 and 0 <= it.label <= MAX_LABEL and 0 <= it.mode <= 3
+            for t in (it.add, it.total):
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == it.H * it.W
+                                     and t.device == out.device and t.data_ptr() % 16 == 0)
+            assert it.labels is None or (it.labels.dtype == torch.int16 and it.labels.is_contiguous() and it.labels.numel() == it.H * it.W
+                                         and it.labels.device == out.device and it.labels.data_ptr() % 8 == 0)
+            d = self._lib.AnnotObj()
+            d.add = it.add.data_ptr() if it.add is not None else None
+            d.total = it.total.data_ptr() if it.total is not None else None
+            d.labels = it.labels.data_ptr() if it.labels is not None else None
+            d.bits = out.data_ptr() + 8 * at[i]
+            d.rec = out.data_ptr() + 8 * _REC * i
+            d.H, d.W, d.label, d.mode = it.H, it.W, it.label, it.mode
+            rows.append(d)
+        raw = bytes((self._lib.AnnotObj * n)(*rows))
+        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
+        self._ops.annot_compose_batched(host.to(self.device, non_blocking=True), n, thr, max(it.H * it.W for it in items))
+        if read is None:
+            return None
+        got = (out if read == "masks" else out[:_REC * n]).cpu().numpy()        # the call's one synchronisation
+        return _decode(got, items, at, read == "masks")
+
+    def extract(self, labels, label):
+        """-> (fp32 [H, W] on the device, record); one read-back (32 bytes)."""
+        out = torch.empty(labels.shape, device=self.device, dtype=torch.float32)
+        rec = torch.empty(8, device=self.device, dtype=torch.int32)
+        self._ops.label_extract(labels, label, out, rec)
+        return out, rec.cpu().numpy()
+
+
+class HostAnnotOps:
+    """The numpy stand-ins behind the same two calls; maps on a device are copied to the host and back."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    @staticmethod
+    def _host(t, kind):
+        return None if t is None else t.detach().cpu().numpy().view(kind)
+
+    def compose(self, items, thr, read):
+        got = []
+        for it in items:
+            add, total, labels = self._host(it.add, np.float32), self._host(it.total, np.float32), self._host(it.labels, np.uint16)
+            words, rec = host_annot_compose(add, total, labels, it.H, it.W, it.label, it.mode, thr)
+            if it.mode & 1 and total is not None and it.total.device.type != "cpu":
+                it.total.copy_(torch.from_numpy(total))
+            if it.mode & 2 and labels is not None and it.labels.device.type != "cpu":
+                it.labels.copy_(torch.from_numpy(labels.view(np.int16)))
+            got.append((rec, unpack_mask(words, it.H, it.W) if read == "masks" else None))
+        return None if read is None else got
+
+    def extract(self, labels, label):
+        host = self._host(labels, np.uint16)
+        out, rec = host_label_extract(host, label)
+        if labels.device.type != "cpu":
+            labels.copy_(torch.from_numpy(host.view(np.int16)))
+        return torch.from_numpy(out).to(labels.device), rec
+
+
+# ------------------------------------------------------------------------------------------------------ the pool
+class _Annotation:
+    """One image: the committed labels and the object being edited."""
+
+    def __init__(self, aid, H, W, device):
+        self.aid, self.H, self.W = aid, H, W
+        self.labels = torch.zeros(H, W, device=device, dtype=torch.int16)      # uint16 values in 16-bit storage
+        self.zeros = torch.zeros(H, W, device=device, dtype=torch.float32)     # (never written)
+        self.object_count, self.records = 0, []
+        self.start()
+
+    def start(self):
+        """A new object.  ``parts`` and ``mask`` are None for zeros / no mask; a tensor that an undo snapshot may hold is
+        never written again (a partial finish makes a new one)."""
+        self.clicker, self.parts, self.mask, self.undo = Clicker(device=None), None, None, []
+
+    @property
+    def total(self):
+        return self.mask if self.mask is not None else self.parts      # R7: the initial mask stands in for the parts
+
+    @property
+    def empty(self):
+        return len(self.clicker) == 0 and self.parts is None and self.mask is None
+
+
+class AnnotationPool:
+    """``ann = AnnotationPool(predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs)``; ``predictor``:
+    any predictor ``SessionPool`` accepts.  ``aid = ann.open(image, seed=None)``; ``ann.click({aid: click, ...}, boxes=None,
+    strokes=None) -> {aid: bool ndarray [H, W]}``; ``undo / partially_finish / finish / set_mask / reopen / label_map /
+    objects / object_count / current_prob / close`` take an ``aid``.
+
+    ``readbacks`` counts the device-to-host synchronisations, the pool's included: a click on objects without parts and
+    initial mask costs the pool's, otherwise one compose launch and one more read-back for those annotations together;
+    ``finish`` one launch and one read-back (32 bytes), ``label_map`` one copy, ``reopen`` one read-back (32 bytes), ``undo``
+    one (the mask), ``partially_finish`` and ``current_prob`` none.  ``ops`` holds the two device operations and may be replaced
+    by ``HostAnnotOps()``."""
+
+    def __init__(self, predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs):
+        if int(max_undo) < 0:
+            raise ValueError("AnnotationPool: max_undo must not be negative")
+        if "max_sessions" in session_pool_kwargs or "pred_thr" in session_pool_kwargs:
+            raise ValueError("AnnotationPool: max_sessions and pred_thr are max_images and prob_thresh here")
+        self.prob_thresh, self.max_images, self.max_undo = float(prob_thresh), int(max_images), int(max_undo)
+        # the pool's own mask is then R1's whenever the object has neither parts nor an initial mask
+        self.pool = SessionPool(predictor, max_sessions=self.max_images, pred_thr=self.prob_thresh, **session_pool_kwargs)
+        self.device = self.pool.device
+        self.ops = DeviceAnnotOps(self.device) if self.device.type == "cuda" else HostAnnotOps(self.device)
+        self._held = {}
+        self._own_readbacks = 0
+
+    readbacks = property(lambda self: self.pool.readbacks + self._own_readbacks)
+    forwards = property(lambda self: self.pool.forwards)
+
+    # ---------------------------------------------------------------------------------------------- images
+    def open(self, image, seed=None):
+        """A new annotation of ``image`` -> its id (the id of its pool session; ids of closed ones are reused)."""
+        try:
+            aid = self.pool.open(image, seed)
+        except ValueError:
+            raise ValueError(f"AnnotationPool: all {self.max_images} images are open") from None
+        H, W = (int(v) for v in self.pool.probs(aid).shape[-2:])
+        self._held[aid] = _Annotation(aid, H, W, self.device)
+        return aid
+
+    def close(self, aid):
+        self._ann(aid)
+        self.pool.close(aid)
+        del self._held[aid]
+
+    def _ann(self, aid):
+        if not isinstance(aid, (int, np.integer)) or aid not in self._held:
+            raise KeyError(f"AnnotationPool: no open annotation {aid!r}")
+        return self._held[aid]
+
+    # ---------------------------------------------------------------------------------------------- the object in progress
+    def _additive(self, a):
+        return self.pool.probs(a.aid)[0, 0] if len(a.clicker) else None     # zeros while the object has no clicks
+
+    def _reset_session(self, a):
+        self.pool.set_states(a.aid, {"roi": None, "box": None, "prev_prediction": a.zeros})
+
+    def _snapshot(self, a):
+        a.undo.append((a.clicker.get_state(), self.pool.get_states(a.aid), a.parts, a.mask))
+        if len(a.undo) > self.max_undo:
+            del a.undo[0]
+
+    def _item(self, a, **more):
+        return _Item(a.H, a.W, add=self._additive(a), total=a.total, **more)
+
+    def _next_label(self, a):
+        if a.object_count + 1 > MAX_LABEL:
+            raise ValueError(f"AnnotationPool: label {a.object_count + 1} does not fit the 16-bit label map")
+        return a.object_count + 1
+
+    def _masks(self, anns):
+        """R1's masks of ``anns`` by one compose launch and one read-back."""
+        got = self.ops.compose([self._item(a) for a in anns], self.prob_thresh, "masks")
+        self._own_readbacks += 1
+        return {a.aid: mask for a, (_, mask) in zip(anns, got)}
+
+    @torch.no_grad()
+    def click(self, clicks, boxes=None, strokes=None):
+        """``clicks``: {aid: Click or (is_positive, (row, col))}, one click per named annotation; ``boxes`` / ``strokes`` are
+        ``SessionPool.predict``'s, keyed by ``aid`` -> {aid: the current object's mask}."""
+        anns = [self._ann(aid) for aid in clicks]
+        new = {}
+        for aid, c in clicks.items():
+            new[aid] = c.copy() if isinstance(c, Click) else Click(bool(c[0]), (int(c[1][0]), int(c[1][1])))
+        for a in anns:
+            self._snapshot(a)
+            a.clicker.add_click(new[a.aid])
+        try:
+            out = self.pool.predict({a.aid: a.clicker for a in anns}, prev_masks={a.aid: a.mask for a in anns if a.mask is not None},
+                                    boxes=boxes, strokes=strokes)
+        except Exception:
+            for a in anns:                   # the pool refuses a call before it changes a session: take the click back
+                a.clicker._remove_last_click()
+                a.undo.pop()
+            raise
+        twice = [a for a in anns if a.mask is not None and len(a.clicker) == 1]
+        if twice:                           # the first click on an initial mask runs again, on the ZoomIn state the first pass left
+            named = {a.aid for a in twice}
+            out.update(self.pool.predict({a.aid: a.clicker for a in twice}, prev_masks={a.aid: a.mask for a in twice},
+                                         boxes={k: v for k, v in (boxes or {}).items() if k in named},
+                                         strokes={k: v for k, v in (strokes or {}).items() if k in named}))
+        composed = [a for a in anns if a.total is not None]
+        if composed:
+            out.update(self._masks(composed))
+        return {a.aid: out[a.aid] for a in anns}
+
+    def undo(self, aid):
+        """Back to before the object's last click or partial finish -> its mask then, or None when there is nothing to undo."""
+        a = self._ann(aid)
+        if not a.undo:
+            return None
+        clicks, states, a.parts, a.mask = a.undo.pop()
+        a.clicker.click_indx_offset = 1 if a.mask is not None else 0
+        a.clicker.set_state(clicks)
+        self.pool.set_states(aid, states)
+        if a.empty:
+            return np.zeros((a.H, a.W), dtype=bool)
+        return self._masks([a])[aid]
+
+    def partially_finish(self, aid):
+        """R4.  No synchronisation: one launch that writes the new parts."""
+        a = self._ann(aid)
+        if a.empty:
+            return
+        self._snapshot(a)
+        parts = a.total.clone() if a.total is not None else torch.zeros_like(a.zeros)
+        if len(a.clicker):
+            self.ops.compose([_Item(a.H, a.W, add=self._additive(a), total=parts, mode=1)], self.prob_thresh, None)
+        a.parts, a.mask = parts, None
+        a.clicker.reset_clicks()
+        a.clicker.click_indx_offset = 0
+        self._reset_session(a)
+
+    def finish(self, aid):
+        """R5 -> the object's record ``dict(label, area, box=(rmin, rmax, cmin, cmax), overwritten)``, None for an empty
+        object.  The box of an object without a pixel is (H, -1, W, -1)."""
+        a = self._ann(aid)
+        if a.empty:
+            return None
+        label = self._next_label(a)
+        (rec, _), = self.ops.compose([self._item(a, labels=a.labels, label=label, mode=2)], self.prob_thresh, "records")
+        self._own_readbacks += 1
+        record = dict(label=label, area=int(rec[0]), box=tuple(int(v) for v in rec[2:6]), overwritten=int(rec[1]))
+        a.object_count = label
+        a.records.append(record)
+        a.start()
+        self._reset_session(a)
+        return dict(record)
+
+    def _as_mask(self, a, mask):
+        if torch.is_tensor(mask):
+            mask = mask.detach()
+        else:
+            mask = torch.from_numpy(np.ascontiguousarray(mask))
+        if tuple(mask.shape) != (a.H, a.W):
+            raise ValueError(f"AnnotationPool: a mask of {tuple(mask.shape)} for an image of {(a.H, a.W)}")
+        return mask.to(self.device).float().contiguous().clone()
+
+    def set_mask(self, aid, mask):
+        """R7: the object in progress is discarded; ``mask`` (bool or float [H, W]) is the new object's initial mask."""
+        a = self._ann(aid)
+        mask = self._as_mask(a, mask)
+        a.start()
+        self._reset_session(a)
+        a.mask = mask
+        a.clicker.click_indx_offset = 1
+
+    def reopen(self, aid, label):
+        """R8.  The record of ``label`` leaves ``objects``; finishing the reopened object appends a new one."""
+        a = self._ann(aid)
+        if not isinstance(label, (int, np.integer)) or not any(r["label"] == label for r in a.records):
+            raise KeyError(f"AnnotationPool: annotation {aid!r} has no object {label!r}")
+        out, rec = self.ops.extract(a.labels, int(label))
+        self._own_readbacks += 1
+        if int(rec[0]) == 0:                # later objects have overwritten all of it: nothing was changed
+            raise KeyError(f"AnnotationPool: no pixel of annotation {aid!r} holds label {label!r} any more")
+        a.records = [r for r in a.records if r["label"] != label]
+        a.start()
+        self._reset_session(a)
+        a.mask = out
+        a.clicker.click_indx_offset = 1
+
+    # ---------------------------------------------------------------------------------------------- results
+    def label_map(self, aid, preview=True):
+        """uint16 [H, W]: the committed labels, with ``preview`` R2's (the object in progress drawn with its future label)."""
+        a = self._ann(aid)
+        labels = a.labels
+        if preview and not a.empty:
+            labels = a.labels.clone()
+            self.ops.compose([self._item(a, labels=labels, label=self._next_label(a), mode=2)], self.prob_thresh, None)
+        self._own_readbacks += 1
+        host = labels.cpu().numpy().view(np.uint16)
+        return host.copy() if labels is a.labels and self.device.type == "cpu" else host
+
+    def objects(self, aid):
+        return [dict(r) for r in self._ann(aid).records]
+
+    def object_count(self, aid):
+        return self._ann(aid).object_count
+
+    def current_prob(self, aid):
+        """R1's ``current``: fp32 [1, 1, H, W] on the device, a map of its own."""
+        a = self._ann(aid)
+        cur = a.total.clone() if a.total is not None else torch.zeros_like(a.zeros)
+        if len(a.clicker):
+            self.ops.compose([_Item(a.H, a.W, add=self._additive(a), total=cur, mode=1)], self.prob_thresh, None)
+        return cur[None, None]

@@ -469,6 +469,22 @@ def session_paste_batched(objs, n, probs, S_h, S_w, pred_thr, box_thr, max_hw, f
               SESSION_PASTE_FORM if form is None else int(form), _stream())
 
 
+def annot_compose_batched(objs, n, thr, max_hw):
+    """n annotations (objs: device array of vpu_annot_obj) composed in one launch: packed mask of max(total, add) > thr and
+    its record, by mode total = max(total, add) and labels = label under the mask (vpu_annot_compose_batched)."""
+    _lib.call("vpu_annot_compose_batched", ptr(objs), n, float(thr), max_hw, _stream())
+
+
+def label_extract(labels, label, out, rec):
+    """out fp32 [H, W] = labels == label, those pixels of ``labels`` (16-bit [H, W]) set to 0, rec int32 [8] = their count and
+    box (vpu_label_extract)."""
+    H, W = labels.shape
+    assert labels.element_size() == 2 and labels.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (H, W)
+    assert rec.dtype == torch.int32 and rec.is_contiguous() and rec.numel() >= 8
+    _lib.call("vpu_label_extract", ptr(labels), ptr(out), ptr(rec), H, W, int(label), _stream())
+
+
 def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
     err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)
