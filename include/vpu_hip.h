@@ -409,6 +409,34 @@ int vpu_annot_compose_batched(const vpu_annot_obj* objs, int32_t n, float thr, i
 /* One annotation: out fp32 [H][W] (16-byte aligned) = labels == label ? 1 : 0, every pixel written; those pixels of labels
  * (uint16 [H][W], 8-byte aligned) become 0; rec = {area, 0, rmin, rmax, cmin, cmax, 0, 0} of them.  1 <= label <= 65535. */
 int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int32_t H, int32_t W, int32_t label, void* stream);
+/* Run-length maps (pvpuformer_amd/isegm/inference/runs.py): COCO's column-major stream i = c * H + r of an [H][W] map of
+ * integer values v; a run starts at i == 0 and wherever v_i != v_{i-1} (the predecessor of (0, c) is (H - 1, c - 1): a value
+ * that continues from the bottom of a column into the top of the next starts no run).  One launch covers n maps of
+ * different sizes:
+ *   kind 0: src fp32 [H][W], 16-byte aligned, v = src > thr ? 1 : 0 (strict, in fp32; NaN is outside the contract);
+ *   kind 1: src uint16 [H][W], 8-byte aligned, v = the label; thr is not read. */
+typedef struct vpu_runs_obj {
+    const void* src;
+    int32_t H, W, kind;
+    float thr;
+} vpu_runs_obj;
+/* A lane walks VPU_RUNS_BAND_ROWS rows of one column, a wave VPU_RUNS_COLS columns; bands = ceil(H / VPU_RUNS_BAND_ROWS).
+ * objs is the DEVICE array of the n descriptors, host_objs the same n descriptors in host memory (the staging buffer they were
+ * copied from): the wrapper reads the sizes, pointers and kinds there, refuses a bad one before any launch (VPU_ERR_ARG: n
+ * outside 1 .. 65535, a NULL src, H or W < 1, H * W >= 2^31, the items' pixels together >= 2^31, a kind other than 0 / 1;
+ * VPU_ERR_ALIGN: a misaligned src) and sizes the grid from them.  scratch: int32 [scratch_len], scratch_len >= n * stride with
+ * stride = the largest W * bands of the items; item k's entry of (column c, band b) is scratch[k * stride + c * bands_k + b].
+ * vpu_runs_count_batched (two launches): scratch = the exclusive prefix sums, over all items in order, of the run starts per
+ * (item, column, band) -- stream order -- and header int32 [n + 1] = the rank of each item's first run, header[n] = the total.
+ * vpu_runs_write_batched (one launch; scratch as the count call left it): entries int32 [cap][2] (8-byte aligned), entry
+ * header[k] + j = (start, value) of item k's j-th run, start relative to the item.  Only ranks below cap are written, with one
+ * 8-byte store each, and nothing else is; cap >= 0, entries may be NULL when cap == 0.  Neither allocates nor synchronises. */
+#define VPU_RUNS_BAND_ROWS 64
+#define VPU_RUNS_COLS 64
+int vpu_runs_count_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, int32_t* scratch,
+                           int64_t scratch_len, int32_t* header, void* stream);
+int vpu_runs_write_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, const int32_t* scratch,
+                           int64_t scratch_len, int32_t* entries, int32_t cap, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

@@ -79,6 +79,11 @@ class AnnotObj(C.Structure):
                 ("H", C.c_int32), ("W", C.c_int32), ("label", C.c_int32), ("mode", C.c_int32)]
 
 
+class RunsObj(C.Structure):
+    """vpu_runs_obj (include/vpu_hip.h): one map of vpu_runs_count_batched / vpu_runs_write_batched."""
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32), ("thr", C.c_float)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -130,6 +135,8 @@ SIGNATURES = {
     "vpu_session_paste_batched": [_P, _I, _P, _I, _I, _F, _F, _I, _I, _P],
     "vpu_annot_compose_batched": [_P, _I, _F, _I, _P],
     "vpu_label_extract": [_P, _P, _P, _I, _I, _I, _P],
+    "vpu_runs_count_batched": [_P, _P, _I, _P, _L, _P, _P],
+    "vpu_runs_write_batched": [_P, _P, _I, _P, _L, _P, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

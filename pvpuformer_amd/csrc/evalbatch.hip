@@ -3,6 +3,8 @@
 // include/vpu_hip.h), so that one launch covers all of them whatever their sizes.  All passes are bandwidth-bound
 // streams over the objects' canvases: 4 pixels per thread (16-byte fp32 / 4-byte uint8 accesses), block-level reduction,
 // one atomic per workgroup and counter.  Kernels neither allocate nor synchronise (hipGraph-capturable).
+#include <cstdio>
+
 #include "vpu_common.h"
 #include "interp_ac.h"
 #include "../../include/vpu_hip.h"
@@ -752,6 +754,116 @@ __global__ __launch_bounds__(256) void label_extract_kernel(uint16_t* __restrict
     annot_reduce(rec, a);
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (8) run-length maps (isegm/inference/runs.py): the (start, value) pairs of COCO's column-major stream i = c * H + r of n maps
+//     of different sizes, v = src > thr (kind 0, fp32) or the 16-bit label (kind 1).  A run starts at i == 0 and wherever
+//     v_i != v_{i-1}; the predecessor of (0, c) is (H - 1, c - 1).
+//
+//     walk: one wave per block; a lane owns a column and walks VPU_RUNS_BAND_ROWS rows of it top to bottom, so a wave's loads
+//     are one row segment of VPU_RUNS_COLS values and the stream predecessor of a pixel is the lane's own previous value: no
+//     transpose, no LDS, no barrier.  One extra load gives the predecessor of the first row the lane visits.  The count form
+//     writes the lane's number of run starts to scratch[item * stride + c * bands + band] (stream order inside an item); the
+//     write form starts from the scanned value there and stores one (start, value) per run start, 8 bytes each.
+template <int KIND>
+__device__ __forceinline__ unsigned runs_value(const void* __restrict__ src, int64_t i, float thr) {
+    if (KIND == 0) return reinterpret_cast<const float*>(src)[i] > thr ? 1u : 0u;
+    return reinterpret_cast<const uint16_t*>(src)[i];
+}
+
+template <int KIND, bool WRITE>
+__device__ __forceinline__ void runs_walk(const vpu_runs_obj& d, int c, int r0, int r1, int* __restrict__ slot,
+                                          int2* __restrict__ entries, int cap) {
+    const int64_t W = d.W;
+    const float thr = d.thr;
+    // the value no pixel has: the first pixel of the stream always starts a run
+    unsigned prev = 0xffffffffu;
+    if (r0 > 0) prev = runs_value<KIND>(d.src, (int64_t)(r0 - 1) * W + c, thr);
+    else if (c > 0) prev = runs_value<KIND>(d.src, (int64_t)(d.H - 1) * W + c - 1, thr);
+    int count = 0;
+    unsigned rank = WRITE ? (unsigned)*slot : 0u;
+    const int start0 = c * d.H;                                       // (host: H * W < 2^31)
+    for (int r = r0; r < r1; r += 8) {
+        unsigned v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = r + u < r1 ? runs_value<KIND>(d.src, (int64_t)(r + u) * W + c, thr) : 0u;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (r + u < r1) {
+                if (v[u] != prev) {
+                    if (WRITE) {
+                        if (rank < (unsigned)cap) entries[rank] = make_int2(start0 + r + u, (int)v[u]);
+                        ++rank;
+                    } else {
+                        ++count;
+                    }
+                }
+                prev = v[u];
+            }
+        }
+    }
+    if (!WRITE) *slot = count;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(VPU_RUNS_COLS) void runs_walk_kernel(const vpu_runs_obj* __restrict__ objs, int bands_max,
+                                                                  int64_t stride, int* __restrict__ scratch,
+                                                                  int2* __restrict__ entries, int cap) {
+    const vpu_runs_obj& d = objs[blockIdx.y];
+    const int bands = (d.H + VPU_RUNS_BAND_ROWS - 1) / VPU_RUNS_BAND_ROWS;
+    const int band = blockIdx.x % bands_max, c = (blockIdx.x / bands_max) * VPU_RUNS_COLS + threadIdx.x;
+    if (band >= bands || c >= d.W) return;
+    const int r0 = band * VPU_RUNS_BAND_ROWS, r1 = min(r0 + VPU_RUNS_BAND_ROWS, d.H);
+    int* slot = scratch + (int64_t)blockIdx.y * stride + (int64_t)c * bands + band;
+    if (d.kind == 0) runs_walk<0, WRITE>(d, c, r0, r1, slot, entries, cap);
+    else runs_walk<1, WRITE>(d, c, r0, r1, slot, entries, cap);
+}
+
+//     scan: ONE workgroup turns the counts of all items into exclusive prefix sums in place, item after item and 4096 entries
+//     per turn (four per thread), and writes header[k] = the rank of item k's first run, header[n] = the total.  No workgroup
+//     waits on another; the array is W * bands entries per item.
+__global__ __launch_bounds__(1024) void runs_scan_kernel(const vpu_runs_obj* __restrict__ objs, int n, int64_t stride,
+                                                         int* __restrict__ scratch, int* __restrict__ header) {
+    __shared__ int wave_sum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int carry = 0;                                                    // the same value in every thread
+    for (int k = 0; k < n; ++k) {
+        if (tid == 0) header[k] = carry;
+        const int64_t len = (int64_t)objs[k].W * ((objs[k].H + VPU_RUNS_BAND_ROWS - 1) / VPU_RUNS_BAND_ROWS);
+        int* base = scratch + (int64_t)k * stride;
+        for (int64_t off = 0; off < len; off += 4096) {
+            const int64_t i0 = off + 4 * tid;
+            int x[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[u] = i0 + u < len ? base[i0 + u] : 0;
+            const int own = x[0] + x[1] + x[2] + x[3];
+            int incl = own;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int up = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += up;
+            }
+            if (lane == 63) wave_sum[wave] = incl;
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                const int s = wave_sum[w];
+                if (w < wave) before += s;
+                all += s;
+            }
+            int at = carry + before + incl - own;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + u < len) base[i0 + u] = at;
+                at += x[u];
+            }
+            carry += all;
+            __syncthreads();                                          // wave_sum is written again in the next turn
+        }
+    }
+    if (tid == 0) header[n] = carry;
+}
+
 }  // namespace
 
 static bool crops_sizes_ok(int32_t ny, int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw) {
@@ -903,4 +1015,79 @@ extern "C" int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int
     const int nb = vpu_grid_for(((long long)H * W + 3) / 4, 256, 1024);
     label_extract_kernel<<<(unsigned)nb, 256, 0, ST>>>(labels, out, rec, H, W, (unsigned)label);
     return vpu_check_launch("vpu_label_extract");
+}
+
+// The launch geometry of (8) from the host's copy of the descriptors, after every check of them: bands_max and cols_max
+// size the grid, stride = the largest W * bands is the distance of two items in scratch.
+struct RunsPlan {
+    int bands_max = 0, groups_max = 0;
+    int64_t stride = 0;
+};
+
+static int runs_plan(const char* who, const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, RunsPlan& p) {
+    char msg[192];
+    if (!objs || !host_objs || n < 1 || n > 65535) {
+        snprintf(msg, sizeof msg, "%s: null descriptors or n (1 <= n <= 65535)", who);
+        vpu_set_error(msg);
+        return VPU_ERR_ARG;
+    }
+    int64_t pixels = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        const vpu_runs_obj& d = host_objs[k];
+        if (!d.src || d.H < 1 || d.W < 1 || (int64_t)d.H * d.W > 0x7fffffffLL || (d.kind != 0 && d.kind != 1)) {
+            snprintf(msg, sizeof msg, "%s: item %d: null src, sizes (H, W >= 1, H * W < 2^31) or kind (0: fp32 > thr, 1: labels)", who, k);
+            vpu_set_error(msg);
+            return VPU_ERR_ARG;
+        }
+        if (reinterpret_cast<uintptr_t>(d.src) % (d.kind == 0 ? 16 : 8)) {
+            snprintf(msg, sizeof msg, "%s: item %d: src not %d-byte aligned", who, k, d.kind == 0 ? 16 : 8);
+            vpu_set_error(msg);
+            return VPU_ERR_ALIGN;
+        }
+        const int bands = (d.H + VPU_RUNS_BAND_ROWS - 1) / VPU_RUNS_BAND_ROWS;
+        const int groups = (d.W + VPU_RUNS_COLS - 1) / VPU_RUNS_COLS;
+        p.bands_max = bands > p.bands_max ? bands : p.bands_max;
+        p.groups_max = groups > p.groups_max ? groups : p.groups_max;
+        p.stride = (int64_t)d.W * bands > p.stride ? (int64_t)d.W * bands : p.stride;
+        pixels += (int64_t)d.H * d.W;
+    }
+    // every rank and every scratch index fits an int32, and so does the grid
+    if (pixels > 0x7fffffffLL || p.stride * n > 0x7fffffffLL || (int64_t)p.bands_max * p.groups_max > 0x7fffffffLL) {
+        snprintf(msg, sizeof msg, "%s: the items together have 2^31 pixels or more", who);
+        vpu_set_error(msg);
+        return VPU_ERR_ARG;
+    }
+    return 0;
+}
+
+extern "C" int vpu_runs_count_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, int32_t* scratch,
+                                      int64_t scratch_len, int32_t* header, void* stream) {
+    vpu_clear_stale_error();
+    RunsPlan p;
+    const int rc = runs_plan("runs_count_batched", objs, host_objs, n, p);
+    if (rc) return rc;
+    if (!scratch || !header || scratch_len < p.stride * n) {
+        vpu_set_error("runs_count_batched: null scratch or header, or scratch_len below n * max(W * bands)");
+        return VPU_ERR_ARG;
+    }
+    runs_walk_kernel<false><<<dim3((unsigned)(p.bands_max * p.groups_max), (unsigned)n), VPU_RUNS_COLS, 0, ST>>>(
+        objs, p.bands_max, p.stride, scratch, nullptr, 0);
+    runs_scan_kernel<<<1, 1024, 0, ST>>>(objs, n, p.stride, scratch, header);
+    return vpu_check_launch("vpu_runs_count_batched");
+}
+
+extern "C" int vpu_runs_write_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, const int32_t* scratch,
+                                      int64_t scratch_len, int32_t* entries, int32_t cap, void* stream) {
+    vpu_clear_stale_error();
+    RunsPlan p;
+    const int rc = runs_plan("runs_write_batched", objs, host_objs, n, p);
+    if (rc) return rc;
+    if (!scratch || scratch_len < p.stride * n || cap < 0 || (cap > 0 && !entries)) {
+        vpu_set_error("runs_write_batched: null scratch or entries, scratch_len below n * max(W * bands), or cap < 0");
+        return VPU_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(entries) % 8) { vpu_set_error("runs_write_batched: entries not 8-byte aligned"); return VPU_ERR_ALIGN; }
+    runs_walk_kernel<true><<<dim3((unsigned)(p.bands_max * p.groups_max), (unsigned)n), VPU_RUNS_COLS, 0, ST>>>(
+        objs, p.bands_max, p.stride, const_cast<int32_t*>(scratch), reinterpret_cast<int2*>(entries), cap);
+    return vpu_check_launch("vpu_runs_write_batched");
 }

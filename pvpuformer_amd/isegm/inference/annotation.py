@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from .clicker import Click, Clicker
+from .runs import KIND_LABELS, DeviceRunOps, HostRunOps
 from .sessions import SessionPool, n_words, pack_mask, unpack_mask
 
 MAX_LABEL = 65535
@@ -186,13 +187,14 @@ class AnnotationPool:
     """``ann = AnnotationPool(predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs)``; ``predictor``:
     any predictor ``SessionPool`` accepts.  ``aid = ann.open(image, seed=None)``; ``ann.click({aid: click, ...}, boxes=None,
     strokes=None) -> {aid: bool ndarray [H, W]}``; ``undo / partially_finish / finish / set_mask / reopen / label_map /
-    objects / object_count / current_prob / close`` take an ``aid``.
+    label_runs / export / objects / object_count / current_prob / close`` take an ``aid``.
 
     ``readbacks`` counts the device-to-host synchronisations, the pool's included: a click on objects without parts and
     initial mask costs the pool's, otherwise one compose launch and one more read-back for those annotations together;
     ``finish`` one launch and one read-back (32 bytes), ``label_map`` one copy, ``reopen`` one read-back (32 bytes), ``undo``
-    one (the mask), ``partially_finish`` and ``current_prob`` none.  ``ops`` holds the two device operations and may be replaced
-    by ``HostAnnotOps()``."""
+    one (the mask), ``partially_finish`` and ``current_prob`` none; ``label_runs`` two (the offsets, then 8 bytes per run) and
+    ``export`` two, none when no object is finished.  ``ops`` holds the two device operations and may be replaced by
+    ``HostAnnotOps()``; ``ops_runs`` holds the run-length encoder and may be replaced by ``HostRunOps()``."""
 
     def __init__(self, predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs):
         if int(max_undo) < 0:
@@ -204,6 +206,7 @@ class AnnotationPool:
         self.pool = SessionPool(predictor, max_sessions=self.max_images, pred_thr=self.prob_thresh, **session_pool_kwargs)
         self.device = self.pool.device
         self.ops = DeviceAnnotOps(self.device) if self.device.type == "cuda" else HostAnnotOps(self.device)
+        self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
         self._held = {}
         self._own_readbacks = 0
 
@@ -374,6 +377,30 @@ class AnnotationPool:
         self._own_readbacks += 1
         host = labels.cpu().numpy().view(np.uint16)
         return host.copy() if labels is a.labels and self.device.type == "cpu" else host
+
+    def label_runs(self, aid, preview=True):
+        """The ``RunMap`` (runs.py) of exactly the array ``label_map(aid, preview)`` returns, built as that method builds it
+        and encoded on the device: two read-backs, the offsets and 8 bytes per run, in place of the 16-bit map."""
+        a = self._ann(aid)
+        labels = a.labels
+        if preview and not a.empty:
+            labels = a.labels.clone()
+            self.ops.compose([self._item(a, labels=labels, label=self._next_label(a), mode=2)], self.prob_thresh, None)
+        rm, = self.ops_runs.encode([(labels, KIND_LABELS, 0.0)])
+        self._own_readbacks += 2
+        return rm
+
+    def export(self, aid):
+        """The finished objects in COCO's form: the records of ``objects(aid)``, each with ``segmentation = dict(size=[H, W],
+        counts=[...])``, the uncompressed run-length encoding of the pixels that hold its label now (an object that later
+        ones have covered keeps its record; its counts are then ``[H * W]``).  ONE encode of the committed label map, without
+        the object in progress: two read-backs.  [] without touching the device when no object is finished."""
+        a = self._ann(aid)
+        if not a.records:
+            return []
+        rm, = self.ops_runs.encode([(a.labels, KIND_LABELS, 0.0)])
+        self._own_readbacks += 2
+        return [dict(r, segmentation=rm.to_coco(r["label"])) for r in a.records]
 
     def objects(self, aid):
         return [dict(r) for r in self._ann(aid).records]

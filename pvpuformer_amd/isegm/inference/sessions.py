@@ -35,6 +35,7 @@ import torch
 
 from ..model.scribble import scribble_profiles
 from .batched import BatchedEvaluator, _load_image, _padded_slot, batchable
+from .runs import KIND_PROB, DeviceRunOps, HostRunOps
 from .transforms import AddHorizontalFlip, Roi, ZoomIn
 
 _REC = 4             # int64 per session record (int32 [8]: area, count, rmin, rmax, cmin, cmax, 0, 0)
@@ -270,10 +271,11 @@ class SessionPool:
 
     ``sid = pool.open(image, seed=None)``; ``pool.predict({sid: clicks, ...}, prev_masks=None, boxes=None, strokes=None) ->
     {sid: bool ndarray [H, W]}``; ``pool.probs(sid)``; ``pool.get_states(sid)`` / ``pool.set_states(sid, st)``;
-    ``pool.close(sid)``.
+    ``pool.close(sid)``; ``pool.mask_runs(sids=None) -> {sid: RunMap}``, the masks as run-length maps (runs.py).
     ``max_batch``: sessions per forward (default ``max_sessions``); a size group with more runs in chunks.
     ``max_stroke_points``: the longest stroke ``predict`` takes.
-    ``readbacks`` counts the device-to-host synchronisations (one per forward round)."""
+    ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``).  ``ops_runs``
+    holds the run-length encoder and may be replaced by ``HostRunOps()``."""
 
     # ZoomIn on the host, from the box read back with the last prediction: BatchedEvaluator's restatement of ZoomIn.transform /
     # _predicted_box / check_possible_recalculation, used as it stands (they read .zoom and a slot's clicks / roi / box / H / W)
@@ -299,6 +301,7 @@ class SessionPool:
         self.prompt_img = int(size[0]) if size is not None else None
         self.device = torch.device(predictor.device)
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
+        self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
         self._slots = [None] * self.max_sessions
         self.readbacks = self.forwards = 0
 
@@ -326,6 +329,19 @@ class SessionPool:
         until the second ``predict`` of that session from now (clone it to keep it longer)."""
         s = self._session(sid)
         return s.canvas[s.prev][None, None]
+
+    def mask_runs(self, sids=None):
+        """{sid: RunMap} of the mask ``probs(sid) > pred_thr`` of the named sessions (default: all open ones), values 0 / 1, so
+        ``rm.to_coco()`` is the session's mask in COCO's uncompressed run-length form.  One encode for all of them: two
+        read-backs (the offsets, then 8 bytes per run).  A session without a prediction yet gives the single run (0, 0)."""
+        if sids is None:
+            sids = [sid for sid, held in enumerate(self._slots) if held is not None]
+        held = [self._session(sid) for sid in sids]
+        if not held:
+            return {}
+        maps = self.ops_runs.encode([(s.canvas[s.prev], KIND_PROB, self.pred_thr) for s in held])
+        self.readbacks += 2
+        return {s.sid: rm for s, rm in zip(held, maps)}
 
     def get_states(self, sid):
         s = self._session(sid)

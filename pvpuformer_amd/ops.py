@@ -485,6 +485,41 @@ def label_extract(labels, label, out, rec):
     _lib.call("vpu_label_extract", ptr(labels), ptr(out), ptr(rec), H, W, int(label), _stream())
 
 
+RUNS_BAND_ROWS = 64         # VPU_RUNS_BAND_ROWS (include/vpu_hip.h): rows of a column that one lane walks
+RUNS_COLS = 64              # VPU_RUNS_COLS: columns per wave
+
+
+def runs_scratch_len(sizes):
+    """Entries of the int32 scratch array of a run-length call over maps of ``sizes`` [(H, W)]: n * the largest W * bands."""
+    return len(sizes) * max(W * ((H + RUNS_BAND_ROWS - 1) // RUNS_BAND_ROWS) for H, W in sizes)
+
+
+def _runs_check(objs, host_objs, n, scratch):
+    nbytes = n * C.sizeof(_lib.RunsObj)
+    assert n >= 1 and objs.is_cuda and objs.is_contiguous() and objs.numel() * objs.element_size() >= nbytes
+    assert not host_objs.is_cuda and host_objs.is_contiguous() and host_objs.numel() * host_objs.element_size() >= nbytes
+    assert scratch.is_cuda and scratch.dtype == torch.int32 and scratch.is_contiguous()
+
+
+def runs_count_batched(objs, host_objs, n, scratch, header):
+    """Run starts of n maps (objs: device array of vpu_runs_obj, host_objs: the host tensor it was copied from) counted per
+    (item, column, band) into ``scratch`` and scanned in place; header int32 [n + 1] = each item's first rank and the total
+    (vpu_runs_count_batched)."""
+    _runs_check(objs, host_objs, n, scratch)
+    assert header.is_cuda and header.dtype == torch.int32 and header.is_contiguous() and header.numel() >= n + 1
+    _lib.call("vpu_runs_count_batched", ptr(objs), ptr(host_objs), n, ptr(scratch), scratch.numel(), ptr(header), _stream())
+
+
+def runs_write_batched(objs, host_objs, n, scratch, entries, cap=None):
+    """The (start, value) pairs of the n maps into entries int32 [*, 2] at the ranks ``runs_count_batched`` left in
+    ``scratch``; ranks at or beyond ``cap`` (default: all of ``entries``) are not written (vpu_runs_write_batched)."""
+    _runs_check(objs, host_objs, n, scratch)
+    assert entries.is_cuda and entries.dtype == torch.int32 and entries.is_contiguous() and entries.dim() == 2 and entries.shape[1] == 2
+    cap = entries.shape[0] if cap is None else int(cap)
+    assert cap <= entries.shape[0]
+    _lib.call("vpu_runs_write_batched", ptr(objs), ptr(host_objs), n, ptr(scratch), scratch.numel(), ptr(entries), cap, _stream())
+
+
 def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
     err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)
