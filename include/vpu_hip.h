@@ -437,6 +437,25 @@ int vpu_runs_count_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_ob
                            int64_t scratch_len, int32_t* header, void* stream);
 int vpu_runs_write_batched(const vpu_runs_obj* objs, const vpu_runs_obj* host_objs, int32_t n, const int32_t* scratch,
                            int64_t scratch_len, int32_t* entries, int32_t cap, void* stream);
+/* The way back: one (start, value) stream per map, the layout vpu_runs_write_batched produces, decoded on the device.  For
+ * the pixel (r, c) of item k, with i = c * H + r and j the last run whose start <= i:
+ *   kind 0: dst fp32 [H][W], 16-byte aligned, dst[r][c] = value_j == label ? 1.0f : 0.0f;
+ *   kind 1: dst uint16 [H][W], 8-byte aligned, dst[r][c] = (uint16) value_j; label is not read.
+ * entries: int32 [n_runs][2] on the device, 8-byte aligned, start relative to the item; a valid stream has entries[0].start == 0,
+ * strictly increasing starts and a last start below H * W.  Every pixel of dst is written exactly once and nothing else is. */
+typedef struct vpu_unrun_obj {
+    void* dst;
+    const int32_t* entries;
+    int32_t H, W, n_runs, kind, label, pad;
+} vpu_unrun_obj;
+/* One launch over n items (a lane walks VPU_RUNS_BAND_ROWS rows of one column, a wave VPU_RUNS_COLS columns, as above; no
+ * scratch).  objs is the DEVICE array of the n descriptors, host_objs the staging copy in host memory: the wrapper reads sizes
+ * and pointers there and refuses before any launch -- VPU_ERR_ARG: n outside 1 .. 65535, a NULL dst or entries, H or W < 1,
+ * H * W >= 2^31, n_runs < 1 or > H * W, a kind other than 0 / 1, kind 0 with a label outside 0 .. 65535, or items whose largest
+ * band count times largest column-group count is 2^31 or more; VPU_ERR_ALIGN: a misaligned dst or entries.  Whatever the entries
+ * hold, only entries[0 .. n_runs) is read and only dst[0 .. H * W) written; starts that do not increase give an unspecified
+ * map.  Neither allocates nor synchronises. */
+int vpu_runs_decode_batched(const vpu_unrun_obj* objs, const vpu_unrun_obj* host_objs, int32_t n, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

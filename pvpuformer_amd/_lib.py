@@ -84,6 +84,12 @@ class RunsObj(C.Structure):
     _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32), ("thr", C.c_float)]
 
 
+class UnrunObj(C.Structure):
+    """vpu_unrun_obj (include/vpu_hip.h): one map of vpu_runs_decode_batched."""
+    _fields_ = [("dst", C.c_void_p), ("entries", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("n_runs", C.c_int32),
+                ("kind", C.c_int32), ("label", C.c_int32), ("pad", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -137,6 +143,7 @@ SIGNATURES = {
     "vpu_label_extract": [_P, _P, _P, _I, _I, _I, _P],
     "vpu_runs_count_batched": [_P, _P, _I, _P, _L, _P, _P],
     "vpu_runs_write_batched": [_P, _P, _I, _P, _L, _P, _I, _P],
+    "vpu_runs_decode_batched": [_P, _P, _I, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

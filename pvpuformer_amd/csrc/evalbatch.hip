@@ -864,6 +864,69 @@ __global__ __launch_bounds__(1024) void runs_scan_kernel(const vpu_runs_obj* __r
     if (tid == 0) header[n] = carry;
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (9) run-length maps back onto the device: n (start, value) streams, the layout (8) writes, decoded into n maps of different
+//     sizes; dst = value == label ? 1.0f : 0.0f (kind 0, fp32) or the value as uint16 (kind 1).
+//
+//     The mirror of (8)'s walk: one wave per block, a lane owns a column and walks VPU_RUNS_BAND_ROWS rows of it top to bottom,
+//     so a wave's stores are one row segment of VPU_RUNS_COLS values.  At its first pixel i0 a lane finds j = the last run whose
+//     start <= i0 by a binary search over the start words; from then on it keeps value_j and entry j + 1 in registers and steps
+//     when i reaches that start -- at most once per pixel, since starts increase strictly -- with one 8-byte load per step.  No
+//     LDS, no barrier, no atomics.
+//     Bounds, whatever the entries hold: j stays in 0 .. n_runs - 1 (the search runs over [0, n_runs), the step stops at the
+//     last run), so only entries[0 .. n_runs) is read; only (r, c) with r < H, c < W is written, each once.
+__device__ __forceinline__ int2 unrun_next(const int2* __restrict__ e, int j, int n_runs) {
+    // the entry after run j; beyond the last run a start no pixel reaches (host: H * W < 2^31)
+    return j + 1 < n_runs ? e[j + 1] : make_int2(0x7fffffff, 0);
+}
+
+template <int KIND>
+__device__ __forceinline__ void unrun_walk(const vpu_unrun_obj& d, int c, int r0, int r1) {
+    const int2* __restrict__ e = reinterpret_cast<const int2*>(d.entries);
+    const int n_runs = d.n_runs, label = d.label;
+    const int64_t W = d.W;
+    const int start0 = c * d.H;                                       // (host: H * W < 2^31)
+    int lo = 0, hi = n_runs;                                          // upper bound of the first pixel over the starts
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (e[mid].x <= start0 + r0) lo = mid + 1;
+        else hi = mid;
+    }
+    int j = max(lo - 1, 0);
+    int value = e[j].y;
+    int2 next = unrun_next(e, j, n_runs);
+    for (int r = r0; r < r1; r += 8) {
+        int v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (r + u < r1 && start0 + r + u >= next.x) {
+                ++j;
+                value = next.y;
+                next = unrun_next(e, j, n_runs);
+            }
+            v[u] = value;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            if (r + u < r1) {
+                const int64_t at = (int64_t)(r + u) * W + c;
+                if (KIND == 0) reinterpret_cast<float*>(d.dst)[at] = v[u] == label ? 1.0f : 0.0f;
+                else reinterpret_cast<uint16_t*>(d.dst)[at] = (uint16_t)v[u];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(VPU_RUNS_COLS) void unrun_walk_kernel(const vpu_unrun_obj* __restrict__ objs, int bands_max) {
+    const vpu_unrun_obj& d = objs[blockIdx.y];
+    const int bands = (d.H + VPU_RUNS_BAND_ROWS - 1) / VPU_RUNS_BAND_ROWS;
+    const int band = blockIdx.x % bands_max, c = (blockIdx.x / bands_max) * VPU_RUNS_COLS + threadIdx.x;
+    if (band >= bands || c >= d.W) return;
+    const int r0 = band * VPU_RUNS_BAND_ROWS, r1 = min(r0 + VPU_RUNS_BAND_ROWS, d.H);
+    if (d.kind == 0) unrun_walk<0>(d, c, r0, r1);
+    else unrun_walk<1>(d, c, r0, r1);
+}
+
 }  // namespace
 
 static bool crops_sizes_ok(int32_t ny, int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw) {
@@ -1090,4 +1153,39 @@ extern "C" int vpu_runs_write_batched(const vpu_runs_obj* objs, const vpu_runs_o
     runs_walk_kernel<true><<<dim3((unsigned)(p.bands_max * p.groups_max), (unsigned)n), VPU_RUNS_COLS, 0, ST>>>(
         objs, p.bands_max, p.stride, const_cast<int32_t*>(scratch), reinterpret_cast<int2*>(entries), cap);
     return vpu_check_launch("vpu_runs_write_batched");
+}
+
+extern "C" int vpu_runs_decode_batched(const vpu_unrun_obj* objs, const vpu_unrun_obj* host_objs, int32_t n, void* stream) {
+    vpu_clear_stale_error();
+    char msg[224];
+    if (!objs || !host_objs || n < 1 || n > 65535) {
+        vpu_set_error("runs_decode_batched: null descriptors or n (1 <= n <= 65535)");
+        return VPU_ERR_ARG;
+    }
+    int bands_max = 0, groups_max = 0;
+    for (int32_t k = 0; k < n; ++k) {
+        const vpu_unrun_obj& d = host_objs[k];
+        if (!d.dst || !d.entries || d.H < 1 || d.W < 1 || (int64_t)d.H * d.W > 0x7fffffffLL || d.n_runs < 1 ||
+            d.n_runs > (int64_t)d.H * d.W || (d.kind != 0 && d.kind != 1) || (d.kind == 0 && (d.label < 0 || d.label > 65535))) {
+            snprintf(msg, sizeof msg, "runs_decode_batched: item %d: null dst or entries, sizes (H, W >= 1, H * W < 2^31), n_runs "
+                     "(1 <= n_runs <= H * W), kind (0: fp32 of value == label, 1: labels) or label (0 <= label <= 65535)", k);
+            vpu_set_error(msg);
+            return VPU_ERR_ARG;
+        }
+        if (reinterpret_cast<uintptr_t>(d.dst) % (d.kind == 0 ? 16 : 8) || reinterpret_cast<uintptr_t>(d.entries) % 8) {
+            snprintf(msg, sizeof msg, "runs_decode_batched: item %d: dst not %d-byte or entries not 8-byte aligned", k, d.kind == 0 ? 16 : 8);
+            vpu_set_error(msg);
+            return VPU_ERR_ALIGN;
+        }
+        const int bands = (d.H + VPU_RUNS_BAND_ROWS - 1) / VPU_RUNS_BAND_ROWS;
+        const int groups = (d.W + VPU_RUNS_COLS - 1) / VPU_RUNS_COLS;
+        bands_max = bands > bands_max ? bands : bands_max;
+        groups_max = groups > groups_max ? groups : groups_max;
+    }
+    if ((int64_t)bands_max * groups_max > 0x7fffffffLL) {
+        vpu_set_error("runs_decode_batched: the largest item's bands x column groups do not fit the grid");
+        return VPU_ERR_ARG;
+    }
+    unrun_walk_kernel<<<dim3((unsigned)(bands_max * groups_max), (unsigned)n), VPU_RUNS_COLS, 0, ST>>>(objs, bands_max);
+    return vpu_check_launch("vpu_runs_decode_batched");
 }

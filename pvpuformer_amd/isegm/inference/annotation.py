@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .clicker import Click, Clicker
-from .runs import KIND_LABELS, DeviceRunOps, HostRunOps
+from .runs import KIND_LABELS, KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map, stack_objects
 from .sessions import SessionPool, n_words, pack_mask, unpack_mask
 
 MAX_LABEL = 65535
@@ -186,7 +186,7 @@ class _Annotation:
 class AnnotationPool:
     """``ann = AnnotationPool(predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs)``; ``predictor``:
     any predictor ``SessionPool`` accepts.  ``aid = ann.open(image, seed=None)``; ``ann.click({aid: click, ...}, boxes=None,
-    strokes=None) -> {aid: bool ndarray [H, W]}``; ``undo / partially_finish / finish / set_mask / reopen / label_map /
+    strokes=None) -> {aid: bool ndarray [H, W]}``; ``undo / partially_finish / finish / set_mask / load / reopen / label_map /
     label_runs / export / objects / object_count / current_prob / close`` take an ``aid``.
 
     ``readbacks`` counts the device-to-host synchronisations, the pool's included: a click on objects without parts and
@@ -194,7 +194,9 @@ class AnnotationPool:
     ``finish`` one launch and one read-back (32 bytes), ``label_map`` one copy, ``reopen`` one read-back (32 bytes), ``undo``
     one (the mask), ``partially_finish`` and ``current_prob`` none; ``label_runs`` two (the offsets, then 8 bytes per run) and
     ``export`` two, none when no object is finished.  ``ops`` holds the two device operations and may be replaced by
-    ``HostAnnotOps()``; ``ops_runs`` holds the run-length encoder and may be replaced by ``HostRunOps()``."""
+    ``HostAnnotOps()``; ``ops_runs`` holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``.
+    ``load(aid, objects)`` and ``set_mask(aid, RunMap or COCO dict)`` bring run-length objects onto the device through
+    ``ops_runs.decode``: one copy up, one launch, no read-back."""
 
     def __init__(self, predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs):
         if int(max_undo) < 0:
@@ -342,10 +344,27 @@ class AnnotationPool:
             raise ValueError(f"AnnotationPool: a mask of {tuple(mask.shape)} for an image of {(a.H, a.W)}")
         return mask.to(self.device).float().contiguous().clone()
 
-    def set_mask(self, aid, mask):
-        """R7: the object in progress is discarded; ``mask`` (bool or float [H, W]) is the new object's initial mask."""
+    def _run_map(self, a, value, label=1):
+        """``value`` (a RunMap or a COCO ``dict(size, counts)``) as a checked RunMap of the image's size."""
+        rm = as_run_map(value, label)
+        if rm.size != (a.H, a.W):
+            raise ValueError(f"AnnotationPool: a map of {rm.size} for an image of {(a.H, a.W)}")
+        return rm
+
+    def set_mask(self, aid, mask, label=1):
+        """R7: the object in progress is discarded; ``mask`` (bool or float [H, W]) is the new object's initial mask.  A
+        ``RunMap`` or a COCO ``dict(size, counts)`` is taken as well: the initial mask is then ``v == label``, decoded on the
+        device from 8 bytes per run -- no raster is uploaded, nothing is read back -- and is bit for bit what
+        ``set_mask(aid, rm.decode() == label)`` gives.  ``label`` is not read for arrays and tensors."""
         a = self._ann(aid)
-        mask = self._as_mask(a, mask)
+        if isinstance(mask, (RunMap, dict)):
+            if not (isinstance(label, (int, np.integer)) and 0 <= label <= MAX_LABEL):
+                raise ValueError(f"AnnotationPool: label {label!r} is not an integer in 0 .. {MAX_LABEL}")
+            rm = self._run_map(a, mask, label)
+            mask = torch.empty(a.H, a.W, device=self.device, dtype=torch.float32)
+            self.ops_runs.decode([(rm, mask, KIND_PROB, int(label))])
+        else:
+            mask = self._as_mask(a, mask)
         a.start()
         self._reset_session(a)
         a.mask = mask
@@ -401,6 +420,39 @@ class AnnotationPool:
         rm, = self.ops_runs.encode([(a.labels, KIND_LABELS, 0.0)])
         self._own_readbacks += 2
         return [dict(r, segmentation=rm.to_coco(r["label"])) for r in a.records]
+
+    def load(self, aid, objects, keep_labels=False):
+        """Finished objects into a fresh annotation -> their records.  ``objects``: a list of ``RunMap``s (a pixel set where
+        ``v != 0``), COCO ``dict(size, counts)``s, or record dicts that carry ``segmentation`` (what ``export`` returns).  Labels
+        are 1 .. K in list order; with ``keep_labels`` each record's own ``label`` (distinct, in 1 .. 65535), and
+        ``object_count`` is then the largest.  Allowed only on an annotation as ``open`` left it.  For 0 <= prob_thresh < 1 the
+        annotation is left exactly as by ``set_mask(aid, raster_k)``, ``finish(aid)`` for each object in turn: later objects
+        overwrite earlier ones, an empty one still takes its label.  The objects are merged on the host from their runs
+        (``runs.stack_objects``), 40 + 8 bytes per run of the merged map go up in one copy and ONE launch decodes them into the
+        label map; nothing is read back.  Every ValueError is raised before anything is changed."""
+        a = self._ann(aid)
+        if a.records or a.object_count or not a.empty:
+            raise ValueError(f"AnnotationPool.load: annotation {aid!r} already has objects or an object in progress")
+        objects = list(objects)
+        if len(objects) > MAX_LABEL:
+            raise ValueError(f"AnnotationPool.load: {len(objects)} objects do not fit the 16-bit label map")
+        maps, labels = [], []
+        for k, obj in enumerate(objects):
+            record = obj if isinstance(obj, dict) and "segmentation" in obj else None
+            maps.append(self._run_map(a, record["segmentation"] if record is not None else obj))
+            if not keep_labels:
+                labels.append(k + 1)
+                continue
+            label = record.get("label") if record is not None else None
+            if not (isinstance(label, (int, np.integer)) and 1 <= label <= MAX_LABEL) or int(label) in labels:
+                raise ValueError(f"AnnotationPool.load: object {k} has no label of its own in 1 .. {MAX_LABEL}, or repeats one")
+            labels.append(int(label))
+        rm, records = stack_objects((a.H, a.W), maps, labels)
+        self.ops_runs.decode([(rm, a.labels, KIND_LABELS, 0)])
+        a.records, a.object_count = records, max(labels, default=0)
+        a.start()
+        self._reset_session(a)
+        return [dict(r) for r in records]
 
     def objects(self, aid):
         return [dict(r) for r in self._ann(aid).records]

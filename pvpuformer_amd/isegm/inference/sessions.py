@@ -35,7 +35,7 @@ import torch
 
 from ..model.scribble import scribble_profiles
 from .batched import BatchedEvaluator, _load_image, _padded_slot, batchable
-from .runs import KIND_PROB, DeviceRunOps, HostRunOps
+from .runs import KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map
 from .transforms import AddHorizontalFlip, Roi, ZoomIn
 
 _REC = 4             # int64 per session record (int32 [8]: area, count, rmin, rmax, cmin, cmax, 0, 0)
@@ -275,7 +275,7 @@ class SessionPool:
     ``max_batch``: sessions per forward (default ``max_sessions``); a size group with more runs in chunks.
     ``max_stroke_points``: the longest stroke ``predict`` takes.
     ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``).  ``ops_runs``
-    holds the run-length encoder and may be replaced by ``HostRunOps()``."""
+    holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``."""
 
     # ZoomIn on the host, from the box read back with the last prediction: BatchedEvaluator's restatement of ZoomIn.transform /
     # _predicted_box / check_possible_recalculation, used as it stands (they read .zoom and a slot's clicks / roi / box / H / W)
@@ -358,6 +358,12 @@ class SessionPool:
 
     # ---------------------------------------------------------------------------------------------- prediction
     def _as_map(self, value, s):
+        if isinstance(value, (RunMap, dict)):       # run-length form: v == 1, decoded on the device from 8 bytes per run
+            rm = as_run_map(value)
+            assert rm.size == (s.H, s.W), "prev_masks: a map of another size than the session's image"
+            out = torch.empty(s.H, s.W, device=self.device, dtype=torch.float32)
+            self.ops_runs.decode([(rm, out, KIND_PROB, 1)])
+            return out
         if not torch.is_tensor(value):
             value = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float32))
         assert value.numel() == s.H * s.W, "prev_masks: a map of another size than the session's image"
@@ -398,7 +404,8 @@ class SessionPool:
     @torch.no_grad()
     def predict(self, clicks, prev_masks=None, boxes=None, strokes=None):
         """``clicks``: {sid: list of Click, or a Clicker}; ``prev_masks``: {sid: map} replaces that session's previous
-        prediction for this call (dropped under ``_net_input``'s cascade rule) -> {sid: bool ndarray [H, W]}, the mask
+        prediction for this call (dropped under ``_net_input``'s cascade rule; a ``RunMap`` or a COCO ``dict(size, counts)``
+        stands for its pixels ``v == 1`` and is decoded through ``ops_runs``) -> {sid: bool ndarray [H, W]}, the mask
         ``probs(sid) > pred_thr``.  Sessions that are not named are untouched.
 
         ``boxes``: {sid: (r0, c0, r1, c1)}, a drawn box in image pixels, inclusive corners in any order.  ``strokes``: {sid:

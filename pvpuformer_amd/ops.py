@@ -520,6 +520,16 @@ def runs_write_batched(objs, host_objs, n, scratch, entries, cap=None):
     _lib.call("vpu_runs_write_batched", ptr(objs), ptr(host_objs), n, ptr(scratch), scratch.numel(), ptr(entries), cap, _stream())
 
 
+def runs_decode_batched(objs, host_objs, n):
+    """n run-length streams decoded into their maps in one launch (objs: device array of vpu_unrun_obj, host_objs: the host
+    tensor it was copied from): fp32 value == label (kind 0) or the 16-bit values (kind 1); every pixel of every ``dst`` is
+    written (vpu_runs_decode_batched)."""
+    nbytes = n * C.sizeof(_lib.UnrunObj)
+    assert n >= 1 and objs.is_cuda and objs.is_contiguous() and objs.numel() * objs.element_size() >= nbytes
+    assert not host_objs.is_cuda and host_objs.is_contiguous() and host_objs.numel() * host_objs.element_size() >= nbytes
+    _lib.call("vpu_runs_decode_batched", ptr(objs), ptr(host_objs), n, _stream())
+
+
 def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
     err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)
