@@ -311,7 +311,8 @@ int vpu_draw_prompt_rows(const int32_t* kinds, const int32_t* boxes, const int32
  * (0 at zero pixels; +inf when there is none), float32(sqrt(float64)) of the exact integer squared distance -- the map
  * whose arg-max the click simulators take (clicker.py:29-56, trainer.py:628-629, 673-674, 736-737).  zero_border != 0:
  * the image is treated as surrounded by zero pixels (the reference pads the mask by one pixel first).
- * scratch: int32 [B][H][W]. */
+ * scratch: int32 [B][H][W].  H <= 32767, W <= 8192, exact over that whole range (the squared distances are unsigned 32-bit:
+ * 32766^2 + 8191^2 fits). */
 int vpu_edt(const uint8_t* mask, int32_t* scratch, float* dist, int32_t B, int32_t H, int32_t W, int32_t zero_border,
             void* stream);
 /* 5 x 5 chamfer transform = cv2.distanceTransform(mask, DIST_L2, 5) of the training simulators (trainer.py:628-629, 673-674,

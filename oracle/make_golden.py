@@ -3,7 +3,7 @@ run-time stand-ins of oracle/ref_import.py) and, in the same run, checks the ora
 (oracle/vpu_oracle.py) against it.  Build-container only; the fixtures it writes are data (inputs +
 expected outputs), never reference source.
 
-    python oracle/make_golden.py            # writes tests/golden/{pue,disk,tiny,vitb,...}.npz, released_config.pth,
+    python oracle/make_golden.py            # writes tests/golden/{pue,disk,prompt_edges,tiny,vitb,...}.npz, released_config.pth,
                                             # shadowed_public_names.json
     python oracle/make_golden.py vitl vith  # the full-size ViT-L / ViT-H fixtures (minutes of CPU, ~20 GB of memory; not
                                             # in the default list)
@@ -322,6 +322,55 @@ def prompt_fixtures(ref_vpu):
     print("disk counts sample0:", ref_d[0].sum(axis=(1, 2)), " half-integer click:", ref_d[2, 0].sum())
 
 
+def prompt_edge_fixtures(ref_vpu):
+    """The rows of tests/prompt_cases.py the reference model can answer itself, on the table's own inputs (tests/prompt_ref.py
+    draws them): _guassinvector_click / _guassinvector_box at its image size, over the coordinates that flip the corner-drop rule
+    and the truncation and over the box sizes where the radius and sigma change; DistMaps over the table's canvases and slot
+    counts.  Inputs and outputs only; the disk maps bit-packed as in disk.npz."""
+    from isegm.model.ops import DistMaps
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import prompt_cases as pc
+    import prompt_ref as pr
+    cfg = vo.make_cfg(embed_dim=128, depth=8, num_heads=4, out_dims=(16, 32, 64, 128), head_channels=32)
+    model, _ = build_reference(cfg, ref_vpu)
+    dm = DistMaps(norm_radius=5, spatial_scale=1.0, cpu_mode=False, use_disks=True)
+
+    def ref_click(p):
+        with torch.no_grad():
+            return model._guassinvector_click(torch.from_numpy(p)).numpy()
+
+    def ref_box(p, b):
+        with torch.no_grad():
+            return model._guassinvector_box(torch.from_numpy(p), torch.from_numpy(b)).numpy()
+    fx = {}
+    for c in pc.CASES:
+        key = pr.golden_key(c)
+        if key is None or key + "_out" in fx:
+            continue
+        inp = pr.inputs(c)
+        s = c.shape
+        if c.entry == "pue":
+            mine = pr.pue_reference(inp, s["n"], s["num_max"], s["img"])
+            ref = pr.pue_reference(inp, s["n"], s["num_max"], s["img"], click=ref_click, box=ref_box)
+            assert ref["rows"].dtype == np.float64 and np.array_equal(mine["box_rows"], ref["box_rows"])
+            click_rows = ~mine["box_rows"]
+            assert np.array_equal(mine["rows"][click_rows], ref["rows"][click_rows]), (key, "PuE click rows are not bit-exact")
+            err = np.abs(mine["rows"] - ref["rows"]).max()
+            assert err <= 1e-7 and np.array_equal(mine["rows"] != 0, ref["rows"] != 0), (key, err)
+            fx[key + "_points"] = inp["points"]
+            if "boxes" in inp:
+                fx[key + "_boxes"] = inp["boxes"]
+            fx[key + "_out"] = ref["rows"]
+        else:
+            with torch.no_grad():
+                ref_d = dm(torch.zeros(s["B"], 3, s["H"], s["W"]), torch.from_numpy(inp["points"])).numpy()
+            assert np.array_equal(pr.disk_reference(inp, s["n"], s["H"], s["W"], 5), ref_d), (key, "disk-map restatement")
+            fx[key + "_points"] = inp["points"]
+            fx[key + "_out"] = np.packbits(ref_d.astype(np.uint8))
+    np.savez_compressed(os.path.join(OUT, "prompt_edges.npz"), **fx)
+    print("prompt_edges:", len(fx), "arrays,", os.path.getsize(os.path.join(OUT, "prompt_edges.npz")), "bytes")
+
+
 def simulator_fixtures():
     """a16 / a18 bookkeeping: the reference's get_next_promts (click slot / order / label-mask / box logic) and
     BasePredictor.get_points_nd (click packing), run on seeded inputs.  OpenCV / skimage calls inside are replaced by the
@@ -584,7 +633,7 @@ def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     ref_vpu, ref_losses = ref_import.import_reference()
-    which = sys.argv[1:] or ["pue", "tiny", "tinyh", "vitl8", "vitb", "sim", "zoom", "lrd", "scribble", "tiny_scribble",
+    which = sys.argv[1:] or ["pue", "prompt_edges", "tiny", "tinyh", "vitl8", "vitb", "sim", "zoom", "lrd", "scribble", "tiny_scribble",
                              "released", "public_names"]
     if "released" in which:
         released_fixture()
@@ -602,6 +651,8 @@ def main():
         simulator_fixtures()
     if "pue" in which:
         prompt_fixtures(ref_vpu)
+    if "prompt_edges" in which:
+        prompt_edge_fixtures(ref_vpu)
     if "tiny" in which:
         cfg = vo.make_cfg(embed_dim=128, depth=8, num_heads=4, out_dims=(16, 32, 64, 128), head_channels=32)
         run_model_fixture("tiny", cfg, 2, ref_vpu, ref_losses)

@@ -605,7 +605,11 @@ __global__ __launch_bounds__(256) void masked_argmax_kernel(const float* __restr
 // d2[x] = min_x' (x - x')^2 + g[x']^2 by direct search (W <= 1024: ~90 M integer ops for a 448 x 448 mask);
 // dist = float(sqrt(double(d2))) -- bit-identical to the float64 transform cast to float32.
 // border: the image is surrounded by zero pixels (the callers' np.pad(mask, 1) without materialising it).
+// EDT_INF: "no zero pixel in this column" of the column pass (a vertical distance, <= 32767 when there is one).
+// EDT_INF2: the same for the squared distances of the row pass, unsigned: above the largest true one the launcher admits
+// (32767^2 + 8191^2 = 1 140 768 770) and still below 2^32 with any dx^2 <= 8191^2 added to it.
 constexpr int EDT_INF = 1 << 28;
+constexpr unsigned EDT_INF2 = 0xF0000000u;
 
 __global__ __launch_bounds__(256) void edt_cols_kernel(const uint8_t* __restrict__ mask, int* __restrict__ g, int H, int W,
                                                        int border) {
@@ -628,28 +632,28 @@ __global__ __launch_bounds__(256) void edt_cols_kernel(const uint8_t* __restrict
 
 __global__ __launch_bounds__(256) void edt_rows_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ g,
                                                        float* __restrict__ dist, int H, int W, int border) {
-    extern __shared__ int gsq[];   // [W]
+    extern __shared__ unsigned gsq[];   // [W]
     const int y = blockIdx.x, b = blockIdx.y;
     const int64_t row = ((int64_t)b * H + y) * W;
     for (int x = threadIdx.x; x < W; x += 256) {
         const int v = g[row + x];
-        gsq[x] = v >= 32768 ? EDT_INF : v * v;
+        gsq[x] = v >= 32768 ? EDT_INF2 : (unsigned)(v * v);
     }
     __syncthreads();
     for (int x = threadIdx.x; x < W; x += 256) {
         float out = 0.f;
         if (mask[row + x]) {
-            int best = EDT_INF;
+            unsigned best = EDT_INF2;
             if (border) {
-                const int l = (x + 1) * (x + 1), r = (W - x) * (W - x);
+                const unsigned l = (unsigned)((x + 1) * (x + 1)), r = (unsigned)((W - x) * (W - x));
                 best = l < r ? l : r;
             }
             for (int xp = 0; xp < W; ++xp) {
                 const int dx = x - xp;
-                const int c = dx * dx + gsq[xp];
+                const unsigned c = (unsigned)(dx * dx) + gsq[xp];
                 best = c < best ? c : best;
             }
-            out = best >= EDT_INF ? INFINITY : (float)sqrt((double)best);
+            out = best >= EDT_INF2 ? INFINITY : (float)sqrt((double)best);
         }
         dist[row + x] = out;
     }
