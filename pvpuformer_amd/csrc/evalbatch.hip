@@ -14,6 +14,145 @@
 namespace {
 
 // -------------------------------------------------------------------------------------------------------------------
+// (0) what the paste (2), session (5) and annotation (7) passes share.
+//
+//     MaskRec<NSUM, GATE>: a thread's share of an int32 [8] record {NSUM pixel counts | rmin, rmax, cmin, cmax | zeros}.  The box
+//     is that of the pixels sum GATE counts, and count(r, c) takes one such pixel.  The three layouts:
+//       paste statistics {intersection, union, count | box}, session {area, count | box}, annotation {area, overwritten | box}.
+//     rec_init writes the empty record {0.. | H, -1, W, -1 | 0..}; rec_reduce adds a block's shares to it: wave xor-shuffles, the
+//     four waves' partials through LDS, then one atomic per block and counter, the box only when the block counted a pixel of it.
+template <int NSUM, int GATE>
+struct MaskRec {
+    int sum[NSUM] = {};
+    int r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
+    __device__ __forceinline__ void count(int r, int c) {
+        ++sum[GATE];
+        r0 = min(r0, r); r1 = max(r1, r); c0 = min(c0, c); c1 = max(c1, c);
+    }
+};
+using PasteRec = MaskRec<3, 2>;
+using SessionRec = MaskRec<2, 1>;
+using AnnotRec = MaskRec<2, 0>;
+
+template <int NSUM>
+__device__ __forceinline__ void rec_init(int* rec, int H, int W) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) rec[k] = 0;
+    rec[NSUM] = H; rec[NSUM + 1] = -1; rec[NSUM + 2] = W; rec[NSUM + 3] = -1;
+}
+
+__device__ __forceinline__ int* rec_of(const vpu_eval_obj& d) { return reinterpret_cast<int*>(d.out + 2); }
+__device__ __forceinline__ int* rec_of(const vpu_session_obj& d) { return d.rec; }
+__device__ __forceinline__ int* rec_of(const vpu_annot_obj& d) { return d.rec; }
+
+template <int NSUM, class D>
+__global__ void rec_init_kernel(const D* __restrict__ objs, int n) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < n) rec_init<NSUM>(rec_of(objs[b]), objs[b].H, objs[b].W);
+}
+
+template <int NSUM, int GATE>
+__device__ __forceinline__ void rec_reduce(int* rec, MaskRec<NSUM, GATE> a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) a.sum[k] += __shfl_xor(a.sum[k], o, 64);
+        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
+        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
+    }
+    __shared__ int red[4][NSUM + 4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) red[wave][k] = a.sum[k];
+        red[wave][NSUM] = a.r0; red[wave][NSUM + 1] = a.r1; red[wave][NSUM + 2] = a.c0; red[wave][NSUM + 3] = a.c1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+#pragma unroll
+            for (int k = 0; k < NSUM; ++k) red[0][k] += red[w][k];
+            red[0][NSUM] = min(red[0][NSUM], red[w][NSUM]); red[0][NSUM + 1] = max(red[0][NSUM + 1], red[w][NSUM + 1]);
+            red[0][NSUM + 2] = min(red[0][NSUM + 2], red[w][NSUM + 2]); red[0][NSUM + 3] = max(red[0][NSUM + 3], red[w][NSUM + 3]);
+        }
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k)
+            if (red[0][k]) atomicAdd(rec + k, red[0][k]);
+        if (red[0][GATE]) {
+            atomicMin(rec + NSUM, red[0][NSUM]); atomicMax(rec + NSUM + 1, red[0][NSUM + 1]);
+            atomicMin(rec + NSUM + 2, red[0][NSUM + 2]); atomicMax(rec + NSUM + 3, red[0][NSUM + 3]);
+        }
+    }
+}
+
+//     roi_value: pixel (r, c) of ZoomIn.inv_transform's canvas: the [S_h, S_w] map src resized to the roi of d (copied when
+//     the roi has the map's size; sh, sw: the steps of that resize) and pasted into zeros.
+template <class D>
+__device__ __forceinline__ float roi_value(const D& d, const float* __restrict__ src, int S_h, int S_w, bool copy, float sh,
+                                           float sw, int r, int c) {
+    if (r >= d.r0 && r <= d.r1 && c >= d.c0 && c <= d.c1)
+        return copy ? src[(int64_t)(r - d.r0) * S_w + (c - d.c0)] : ac_sample(src, S_w, S_h, S_w, sh, sw, r - d.r0, c - d.c0);
+    return 0.f;
+}
+
+//     The packed mask: pixel i is bit i & 63 of word i >> 6.  With four pixels per lane a wave covers 256 pixels = 4 words per
+//     turn k; lanes 16j .. 16j + 15 hold the nibbles of word 4k + j, joined by four xor-shuffles inside the 16-lane group, whose
+//     first lane stores the word: every word is written once with a plain store (no atomics, no zero-fill first).  All 64
+//     lanes must call it.
+__device__ __forceinline__ void quad_word_store(uint64_t* __restrict__ bits, int64_t k, int lane, unsigned nib, int64_t words) {
+    unsigned long long word = (unsigned long long)nib << (4 * (lane & 15));
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
+    const int64_t at = (k << 2) + (lane >> 4);
+    if ((lane & 15) == 0 && at < words) bits[at] = word;
+}
+
+//     load4 / store4: the four pixels from i0 on of a flat [HW] map, fp32 (16-byte aligned) or 16-bit labels (8-byte aligned): one
+//     access when the quad is whole, else the pixels below HW one by one (the quad that holds the last HW % 4 pixels, or none).
+//     The label store writes a whole quad as it stands and, of a partial one, only the pixels whose bit is set in nib.
+__device__ __forceinline__ void load4(const float* p, int64_t i0, int64_t HW, float (&v)[4]) {
+    if (i0 + 3 < HW) {
+        const float4 f = *reinterpret_cast<const float4*>(p + i0);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u < HW) v[u] = p[i0 + u];
+    }
+}
+
+__device__ __forceinline__ void load4(const uint16_t* p, int64_t i0, int64_t HW, unsigned (&v)[4]) {
+    if (i0 + 3 < HW) {
+        const uint2 q = *reinterpret_cast<const uint2*>(p + i0);
+        v[0] = q.x & 0xffffu; v[1] = q.x >> 16; v[2] = q.y & 0xffffu; v[3] = q.y >> 16;
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u < HW) v[u] = p[i0 + u];
+    }
+}
+
+__device__ __forceinline__ void store4(float* p, int64_t i0, int64_t HW, const float (&v)[4]) {
+    if (i0 + 3 < HW) {
+        *reinterpret_cast<float4*>(p + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u < HW) p[i0 + u] = v[u];
+    }
+}
+
+__device__ __forceinline__ void store4(uint16_t* p, int64_t i0, int64_t HW, const unsigned (&v)[4], unsigned nib) {
+    if (i0 + 3 < HW) {
+        *reinterpret_cast<uint2*>(p + i0) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (nib & (1u << u)) p[i0 + u] = (uint16_t)v[u];
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------------
 // (1) network input: crop_resize(cat(image, prev), roi, (S_h, S_w)) of object b into batch slot d.src and, with flip, its
 //     mirror image into slot n + d.src (AddHorizontalFlip on a batch: [straight..., mirrored...]).  A crop already of the
 //     output size is copied, as crop_resize does (it clones instead of resizing).  4 output pixels per thread along a row.
@@ -48,35 +187,18 @@ __global__ __launch_bounds__(256) void roi_resize_kernel(const vpu_eval_obj* __r
 //     probability map d.src resized to the roi's (h, w) and pasted into zeros, the mask canvas > pred_thr, the IoU counts
 //     of that mask against gt inside valid (utils.get_iou), and the box of canvas > box_thr (vpu_mask_bbox without the
 //     clicks: the host joins them, it knows the click of the next step only after this read-back).
-//     stats (int32 view of d.out + 2): {intersection, union, count, rmin, rmax, cmin, cmax, -}, set by paste_init_kernel.
-struct PasteAcc {
-    int inter = 0, uni = 0, cnt = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
-};
-
+//     stats (int32 view of d.out + 2): PasteRec, {intersection, union, count, rmin, rmax, cmin, cmax, 0}.
 __device__ __forceinline__ void paste_pixel(const vpu_eval_obj& d, const float* __restrict__ src, int S_h, int S_w, bool copy,
-                                            float sh, float sw, int h, int w, float pred_thr, float box_thr, int64_t i,
-                                            uint8_t g, uint8_t valid, float& v, uint8_t& m, PasteAcc& a) {
+                                            float sh, float sw, float pred_thr, float box_thr, int64_t i, uint8_t g,
+                                            uint8_t valid, float& v, uint8_t& m, PasteRec& a) {
     const int r = (int)(i / d.W), c = (int)(i - (int64_t)r * d.W);
-    v = 0.f;
-    if (r >= d.r0 && r <= d.r1 && c >= d.c0 && c <= d.c1)
-        v = copy ? src[(int64_t)(r - d.r0) * S_w + (c - d.c0)] : ac_sample(src, S_w, S_h, S_w, sh, sw, r - d.r0, c - d.c0);
+    v = roi_value(d, src, S_h, S_w, copy, sh, sw, r, c);
     m = v > pred_thr ? 1 : 0;
     if (valid) {
-        a.inter += (m && g) ? 1 : 0;
-        a.uni += (m || g) ? 1 : 0;
+        a.sum[0] += (m && g) ? 1 : 0;                    // intersection
+        a.sum[1] += (m || g) ? 1 : 0;                    // union
     }
-    if (v > box_thr) {
-        ++a.cnt;
-        a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
-    }
-}
-
-__global__ void paste_init_kernel(const vpu_eval_obj* __restrict__ objs, int n) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= n) return;
-    const vpu_eval_obj& d = objs[b];
-    int* s = reinterpret_cast<int*>(d.out + 2);
-    s[0] = 0; s[1] = 0; s[2] = 0; s[3] = d.H; s[4] = -1; s[5] = d.W; s[6] = -1; s[7] = 0;
+    if (v > box_thr) a.count(r, c);
 }
 
 __global__ __launch_bounds__(256) void roi_paste_kernel(const vpu_eval_obj* __restrict__ objs, const float* __restrict__ probs,
@@ -88,53 +210,26 @@ __global__ __launch_bounds__(256) void roi_paste_kernel(const vpu_eval_obj* __re
     const float sh = ac_scale(S_h, h), sw = ac_scale(S_w, w);
     const float* src = probs + (int64_t)d.src * S_h * S_w;
     const int64_t HW = (int64_t)d.H * d.W, quads = HW / 4;
-    PasteAcc a;
+    PasteRec a;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
         const uchar4 g = *reinterpret_cast<const uchar4*>(d.gt + 4 * q);
         const uchar4 vl = *reinterpret_cast<const uchar4*>(d.valid + 4 * q);
         float v[4]; uint8_t m[4];
-        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 0, g.x, vl.x, v[0], m[0], a);
-        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 1, g.y, vl.y, v[1], m[1], a);
-        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 2, g.z, vl.z, v[2], m[2], a);
-        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, 4 * q + 3, g.w, vl.w, v[3], m[3], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, pred_thr, box_thr, 4 * q + 0, g.x, vl.x, v[0], m[0], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, pred_thr, box_thr, 4 * q + 1, g.y, vl.y, v[1], m[1], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, pred_thr, box_thr, 4 * q + 2, g.z, vl.z, v[2], m[2], a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, pred_thr, box_thr, 4 * q + 3, g.w, vl.w, v[3], m[3], a);
         *reinterpret_cast<float4*>(d.canvas + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
         *reinterpret_cast<uchar4*>(d.mask + 4 * q) = make_uchar4(m[0], m[1], m[2], m[3]);
     }
     if (blockIdx.x == 0 && threadIdx.x < (int)(HW - 4 * quads)) {        // the last HW % 4 pixels
         const int64_t i = 4 * quads + threadIdx.x;
         float v; uint8_t m;
-        paste_pixel(d, src, S_h, S_w, copy, sh, sw, h, w, pred_thr, box_thr, i, d.gt[i], d.valid[i], v, m, a);
+        paste_pixel(d, src, S_h, S_w, copy, sh, sw, pred_thr, box_thr, i, d.gt[i], d.valid[i], v, m, a);
         d.canvas[i] = v;
         d.mask[i] = m;
     }
-    // block reduction: wave shuffles, then the four waves' partials through LDS; one atomic per block and counter
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a.inter += __shfl_xor(a.inter, o, 64); a.uni += __shfl_xor(a.uni, o, 64); a.cnt += __shfl_xor(a.cnt, o, 64);
-        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
-        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
-    }
-    __shared__ int red[4][7];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = a.inter; red[wave][1] = a.uni; red[wave][2] = a.cnt;
-        red[wave][3] = a.r0; red[wave][4] = a.r1; red[wave][5] = a.c0; red[wave][6] = a.c1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            red[0][0] += red[k][0]; red[0][1] += red[k][1]; red[0][2] += red[k][2];
-            red[0][3] = min(red[0][3], red[k][3]); red[0][4] = max(red[0][4], red[k][4]);
-            red[0][5] = min(red[0][5], red[k][5]); red[0][6] = max(red[0][6], red[k][6]);
-        }
-        int* s = reinterpret_cast<int*>(d.out + 2);
-        if (red[0][0]) atomicAdd(s + 0, red[0][0]);
-        if (red[0][1]) atomicAdd(s + 1, red[0][1]);
-        if (red[0][2]) {
-            atomicAdd(s + 2, red[0][2]);
-            atomicMin(s + 3, red[0][3]); atomicMax(s + 4, red[0][4]); atomicMin(s + 5, red[0][5]); atomicMax(s + 6, red[0][6]);
-        }
-    }
+    rec_reduce(rec_of(d), a);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -352,65 +447,17 @@ __global__ __launch_bounds__(256) void box_finish_kernel(const vpu_box_row* __re
 }
 
 // -------------------------------------------------------------------------------------------------------------------
-// (5) interactive sessions (isegm/inference/sessions.py): the paste of (2) without ground truth, plus what the caller of
+// (5) interactive sessions (isegm/inference/sessions.py): (2)'s canvas without ground truth, plus what the caller of
 //     a click wants back: the mask canvas > pred_thr at one bit per pixel, its area, and the ZoomIn box of canvas > box_thr.
-//     rec (int32 [8]): {area, count, rmin, rmax, cmin, cmax, 0, 0}, set by session_init_kernel.
-//     Pixel i is bit i & 63 of word i >> 6: 64 consecutive pixels make a word, and a wave has 64 lanes, so every word is
-//     produced inside one wave and written once with a plain store (no atomics on the packed buffer, no zero-fill first).
-struct SessionAcc {
-    int area = 0, cnt = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
-};
-
-// canvas value of pixel i: paste_pixel's expression, so the canvas has vpu_roi_paste_batched's bits
+//     rec (int32 [8]): SessionRec, {area, count, rmin, rmax, cmin, cmax, 0, 0}.
+//     64 consecutive pixels make a word of the packed mask, and a wave has 64 lanes, so every word is produced inside one
+//     wave and written once with a plain store (no atomics on the packed buffer, no zero-fill first).
 __device__ __forceinline__ float session_pixel(const vpu_session_obj& d, const float* __restrict__ src, int S_h, int S_w, bool copy,
-                                               float sh, float sw, float box_thr, int64_t i, SessionAcc& a) {
+                                               float sh, float sw, float box_thr, int64_t i, SessionRec& a) {
     const int r = (int)(i / d.W), c = (int)(i - (int64_t)r * d.W);
-    float v = 0.f;
-    if (r >= d.r0 && r <= d.r1 && c >= d.c0 && c <= d.c1)
-        v = copy ? src[(int64_t)(r - d.r0) * S_w + (c - d.c0)] : ac_sample(src, S_w, S_h, S_w, sh, sw, r - d.r0, c - d.c0);
-    if (v > box_thr) {
-        ++a.cnt;
-        a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
-    }
+    const float v = roi_value(d, src, S_h, S_w, copy, sh, sw, r, c);
+    if (v > box_thr) a.count(r, c);
     return v;
-}
-
-__global__ void session_init_kernel(const vpu_session_obj* __restrict__ objs, int n) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= n) return;
-    const vpu_session_obj& d = objs[b];
-    int* s = d.rec;
-    s[0] = 0; s[1] = 0; s[2] = d.H; s[3] = -1; s[4] = d.W; s[5] = -1; s[6] = 0; s[7] = 0;
-}
-
-// block reduction as in roi_paste_kernel: wave shuffles, the four waves' partials through LDS, one atomic per block and counter
-__device__ __forceinline__ void session_reduce(const vpu_session_obj& d, SessionAcc a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a.area += __shfl_xor(a.area, o, 64); a.cnt += __shfl_xor(a.cnt, o, 64);
-        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
-        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
-    }
-    __shared__ int red[4][6];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = a.area; red[wave][1] = a.cnt;
-        red[wave][2] = a.r0; red[wave][3] = a.r1; red[wave][4] = a.c0; red[wave][5] = a.c1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            red[0][0] += red[k][0]; red[0][1] += red[k][1];
-            red[0][2] = min(red[0][2], red[k][2]); red[0][3] = max(red[0][3], red[k][3]);
-            red[0][4] = min(red[0][4], red[k][4]); red[0][5] = max(red[0][5], red[k][5]);
-        }
-        int* s = d.rec;
-        if (red[0][0]) atomicAdd(s + 0, red[0][0]);
-        if (red[0][1]) {
-            atomicAdd(s + 1, red[0][1]);
-            atomicMin(s + 2, red[0][2]); atomicMax(s + 3, red[0][3]); atomicMin(s + 4, red[0][4]); atomicMax(s + 5, red[0][5]);
-        }
-    }
 }
 
 // form 0: one pixel per lane; a wave's ballot over its 64 consecutive pixels is the word.  The loop runs over words and its
@@ -425,7 +472,7 @@ __global__ __launch_bounds__(256) void session_paste_ballot_kernel(const vpu_ses
     const float* src = probs + (int64_t)d.src * S_h * S_w;
     const int64_t HW = (int64_t)d.H * d.W, words = (HW + 63) >> 6;
     const int lane = threadIdx.x & 63;
-    SessionAcc a;
+    SessionRec a;
     for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < words; k += (int64_t)gridDim.x * 4) {
         const int64_t i = (k << 6) + lane;
         bool m = false;
@@ -433,16 +480,15 @@ __global__ __launch_bounds__(256) void session_paste_ballot_kernel(const vpu_ses
             const float v = session_pixel(d, src, S_h, S_w, copy, sh, sw, box_thr, i, a);
             d.canvas[i] = v;
             m = v > pred_thr;
-            a.area += m ? 1 : 0;
+            a.sum[0] += m ? 1 : 0;                                    // area
         }
         const unsigned long long word = __ballot(m);
         if (lane == 0) d.bits[k] = word;
     }
-    session_reduce(d, a);
+    rec_reduce(d.rec, a);
 }
 
-// form 1: four pixels per lane (one 16-byte canvas store); a wave covers 256 pixels = 4 words per turn, lanes 16j..16j+15 hold
-// the nibbles of word j, joined by four xor-shuffles inside the 16-lane group; the group's first lane stores the word
+// form 1: four pixels per lane (one 16-byte canvas store) and quad_word_store's four words per wave and turn
 __global__ __launch_bounds__(256) void session_paste_quad_kernel(const vpu_session_obj* __restrict__ objs,
                                                                  const float* __restrict__ probs, int S_h, int S_w,
                                                                  float pred_thr, float box_thr) {
@@ -453,7 +499,7 @@ __global__ __launch_bounds__(256) void session_paste_quad_kernel(const vpu_sessi
     const float* src = probs + (int64_t)d.src * S_h * S_w;
     const int64_t HW = (int64_t)d.H * d.W, words = (HW + 63) >> 6, turns = (HW + 255) >> 8;
     const int lane = threadIdx.x & 63;
-    SessionAcc a;
+    SessionRec a;
     for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < turns; k += (int64_t)gridDim.x * 4) {
         const int64_t i0 = (k << 8) + 4 * lane;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -462,23 +508,13 @@ __global__ __launch_bounds__(256) void session_paste_quad_kernel(const vpu_sessi
         for (int u = 0; u < 4; ++u) {
             if (i0 + u < HW) {
                 v[u] = session_pixel(d, src, S_h, S_w, copy, sh, sw, box_thr, i0 + u, a);
-                if (v[u] > pred_thr) { nib |= 1u << u; ++a.area; }
+                if (v[u] > pred_thr) { nib |= 1u << u; ++a.sum[0]; }      // area
             }
         }
-        if (i0 + 3 < HW) {
-            *reinterpret_cast<float4*>(d.canvas + i0) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {                                                  // the quad that holds the last H * W % 4 pixels
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i0 + u < HW) d.canvas[i0 + u] = v[u];
-        }
-        unsigned long long word = (unsigned long long)nib << (4 * (lane & 15));
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
-        const int64_t at = (k << 2) + (lane >> 4);
-        if ((lane & 15) == 0 && at < words) d.bits[at] = word;
+        store4(d.canvas, i0, HW, v);
+        quad_word_store(d.bits, k, lane, nib, words);
     }
-    session_reduce(d, a);
+    rec_reduce(d.rec, a);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -574,60 +610,15 @@ __global__ __launch_bounds__(256) void crops_blend_kernel(const float* __restric
 // -------------------------------------------------------------------------------------------------------------------
 // (7) multi-object annotation (isegm/inference/annotation.py): the object being edited is cur = max(total, add) of two fp32
 //     maps (the finished parts and the session's prediction), its mask cur > thr.  One launch composes n annotations of
-//     different sizes: the packed mask in (5)'s bit order, rec = {area, overwritten, rmin, rmax, cmin, cmax, 0, 0}, and by
-//     mode total = cur (bit 0) and labels = label where the mask is set (bit 1).  The quad form of (5): four pixels per lane,
-//     16-byte loads of both maps, the four labels of a quad in one 8-byte load and, when the mask touches them, one store;
-//     the quad is owned by its lane, so the pixels whose bit is clear are written back as they were read.
-struct AnnotAcc {
-    int area = 0, over = 0, r0 = 0x7fffffff, r1 = -1, c0 = 0x7fffffff, c1 = -1;
-};
-
-__device__ __forceinline__ void annot_rec_init(int* s, int H, int W) {
-    s[0] = 0; s[1] = 0; s[2] = H; s[3] = -1; s[4] = W; s[5] = -1; s[6] = 0; s[7] = 0;
-}
-
-__global__ void annot_init_kernel(const vpu_annot_obj* __restrict__ objs, int n) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= n) return;
-    annot_rec_init(objs[b].rec, objs[b].H, objs[b].W);
-}
-
-__global__ void annot_init_one_kernel(int* rec, int H, int W) { annot_rec_init(rec, H, W); }
-
-// session_reduce's block reduction; the box is that of the mask, so it is merged whenever the block has mask pixels
-__device__ __forceinline__ void annot_reduce(int* s, AnnotAcc a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a.area += __shfl_xor(a.area, o, 64); a.over += __shfl_xor(a.over, o, 64);
-        a.r0 = min(a.r0, __shfl_xor(a.r0, o, 64)); a.r1 = max(a.r1, __shfl_xor(a.r1, o, 64));
-        a.c0 = min(a.c0, __shfl_xor(a.c0, o, 64)); a.c1 = max(a.c1, __shfl_xor(a.c1, o, 64));
-    }
-    __shared__ int red[4][6];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave][0] = a.area; red[wave][1] = a.over;
-        red[wave][2] = a.r0; red[wave][3] = a.r1; red[wave][4] = a.c0; red[wave][5] = a.c1;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            red[0][0] += red[k][0]; red[0][1] += red[k][1];
-            red[0][2] = min(red[0][2], red[k][2]); red[0][3] = max(red[0][3], red[k][3]);
-            red[0][4] = min(red[0][4], red[k][4]); red[0][5] = max(red[0][5], red[k][5]);
-        }
-        if (red[0][1]) atomicAdd(s + 1, red[0][1]);
-        if (red[0][0]) {
-            atomicAdd(s + 0, red[0][0]);
-            atomicMin(s + 2, red[0][2]); atomicMax(s + 3, red[0][3]); atomicMin(s + 4, red[0][4]); atomicMax(s + 5, red[0][5]);
-        }
-    }
-}
+//     different sizes: the packed mask, rec = AnnotRec, {area, overwritten, rmin, rmax, cmin, cmax, 0, 0}, and by mode
+//     total = cur (bit 0) and labels = label where the mask is set (bit 1).  Four pixels per lane: 16-byte loads of both maps,
+//     the four labels of a quad in one 8-byte load and, when the mask touches them, one store; the quad is owned by its lane,
+//     so the pixels whose bit is clear are written back as they were read.
 
 // the mask pixel (r, c) u places after the quad's first pixel (r0, c0): a quad may span several rows when W < 4
-__device__ __forceinline__ void annot_count(AnnotAcc& a, int r, int c, int W) {
+__device__ __forceinline__ void annot_count(AnnotRec& a, int r, int c, int W) {
     while (c >= W) { c -= W; ++r; }
-    ++a.area;
-    a.r0 = min(a.r0, r); a.r1 = max(a.r1, r); a.c0 = min(a.c0, c); a.c1 = max(a.c1, c);
+    a.count(r, c);
 }
 
 __global__ __launch_bounds__(256) void annot_compose_kernel(const vpu_annot_obj* __restrict__ objs, float thr) {
@@ -637,35 +628,14 @@ __global__ __launch_bounds__(256) void annot_compose_kernel(const vpu_annot_obj*
     const int lane = threadIdx.x & 63;
     const bool put_total = (d.mode & 1) && d.total, put_labels = (d.mode & 2) && d.labels;
     const unsigned label = (unsigned)d.label & 0xffffu;
-    AnnotAcc a;
+    AnnotRec a;
     for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < turns; k += (int64_t)gridDim.x * 4) {
         const int64_t i0 = (k << 8) + 4 * lane;
-        const bool full = i0 + 3 < HW;
         float t[4] = {0.f, 0.f, 0.f, 0.f}, ad[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned lb[4] = {0u, 0u, 0u, 0u};
-        if (full) {
-            if (d.total) {
-                const float4 f = *reinterpret_cast<const float4*>(d.total + i0);
-                t[0] = f.x; t[1] = f.y; t[2] = f.z; t[3] = f.w;
-            }
-            if (d.add) {
-                const float4 f = *reinterpret_cast<const float4*>(d.add + i0);
-                ad[0] = f.x; ad[1] = f.y; ad[2] = f.z; ad[3] = f.w;
-            }
-            if (d.labels) {
-                const uint2 q = *reinterpret_cast<const uint2*>(d.labels + i0);
-                lb[0] = q.x & 0xffffu; lb[1] = q.x >> 16; lb[2] = q.y & 0xffffu; lb[3] = q.y >> 16;
-            }
-        } else {                                                      // the quad that holds the last H * W % 4 pixels, or none
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (i0 + u < HW) {
-                    if (d.total) t[u] = d.total[i0 + u];
-                    if (d.add) ad[u] = d.add[i0 + u];
-                    if (d.labels) lb[u] = d.labels[i0 + u];
-                }
-            }
-        }
+        if (d.total) load4(d.total, i0, HW, t);
+        if (d.add) load4(d.add, i0, HW, ad);
+        if (d.labels) load4(d.labels, i0, HW, lb);
         unsigned nib = 0;
         if (i0 < HW) {
             const int r0 = (int)(i0 / d.W), c0 = (int)(i0 - (int64_t)r0 * d.W);
@@ -676,56 +646,30 @@ __global__ __launch_bounds__(256) void annot_compose_kernel(const vpu_annot_obj*
                     if (t[u] > thr) {
                         nib |= 1u << u;
                         annot_count(a, r0, c0 + u, d.W);
-                        if (lb[u] != 0u && lb[u] != label) ++a.over;
+                        if (lb[u] != 0u && lb[u] != label) ++a.sum[1];        // overwritten
                         lb[u] = label;
                     }
                 }
             }
         }
-        if (put_total) {
-            if (full) {
-                *reinterpret_cast<float4*>(d.total + i0) = make_float4(t[0], t[1], t[2], t[3]);
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (i0 + u < HW) d.total[i0 + u] = t[u];
-            }
-        }
-        if (put_labels && nib) {
-            if (full) {
-                *reinterpret_cast<uint2*>(d.labels + i0) = make_uint2(lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16));
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (nib & (1u << u)) d.labels[i0 + u] = (uint16_t)lb[u];
-            }
-        }
-        unsigned long long word = (unsigned long long)nib << (4 * (lane & 15));
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) word |= __shfl_xor(word, o, 64);
-        const int64_t at = (k << 2) + (lane >> 4);
-        if ((lane & 15) == 0 && at < words) d.bits[at] = word;
+        if (put_total) store4(d.total, i0, HW, t);
+        if (put_labels && nib) store4(d.labels, i0, HW, lb, nib);
+        quad_word_store(d.bits, k, lane, nib, words);
     }
-    annot_reduce(d.rec, a);
+    rec_reduce(d.rec, a);
 }
 
-// out = (labels == label) ? 1 : 0, and those label pixels become 0: the mask a committed object is reopened with
+__global__ void rec_init_one_kernel(int* rec, int H, int W) { rec_init<2>(rec, H, W); }
+
+// out = (labels == label) ? 1 : 0, and those label pixels become 0: the mask a committed object is reopened with; rec: AnnotRec
 __global__ __launch_bounds__(256) void label_extract_kernel(uint16_t* __restrict__ labels, float* __restrict__ out,
                                                             int* __restrict__ rec, int H, int W, unsigned label) {
     const int64_t HW = (int64_t)H * W, quads = (HW + 3) >> 2;
-    AnnotAcc a;
+    AnnotRec a;
     for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < quads; k += (int64_t)gridDim.x * 256) {
         const int64_t i0 = k << 2;
-        const bool full = i0 + 3 < HW;
         unsigned lb[4] = {0u, 0u, 0u, 0u};
-        if (full) {
-            const uint2 q = *reinterpret_cast<const uint2*>(labels + i0);
-            lb[0] = q.x & 0xffffu; lb[1] = q.x >> 16; lb[2] = q.y & 0xffffu; lb[3] = q.y >> 16;
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i0 + u < HW) lb[u] = labels[i0 + u];
-        }
+        load4(labels, i0, HW, lb);
         const int r0 = (int)(i0 / W), c0 = (int)(i0 - (int64_t)r0 * W);
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned nib = 0;
@@ -738,20 +682,10 @@ __global__ __launch_bounds__(256) void label_extract_kernel(uint16_t* __restrict
                 annot_count(a, r0, c0 + u, W);
             }
         }
-        if (full) {
-            *reinterpret_cast<float4*>(out + i0) = make_float4(v[0], v[1], v[2], v[3]);
-            if (nib) *reinterpret_cast<uint2*>(labels + i0) = make_uint2(lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16));
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (i0 + u < HW) {
-                    out[i0 + u] = v[u];
-                    if (nib & (1u << u)) labels[i0 + u] = 0;
-                }
-            }
-        }
+        store4(out, i0, HW, v);
+        if (nib) store4(labels, i0, HW, lb, nib);
     }
-    annot_reduce(rec, a);
+    rec_reduce(rec, a);
 }
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -969,7 +903,7 @@ extern "C" int vpu_session_paste_batched(const vpu_session_obj* objs, int32_t n,
         vpu_set_error("session_paste_batched: sizes (1 <= n <= 65535) or form (0: ballot, 1: quads)");
         return VPU_ERR_ARG;
     }
-    session_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    rec_init_kernel<2><<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
     const int nb = vpu_grid_for(max_hw, 1024, 128);
     if (form == 0)
         session_paste_ballot_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, probs, S_h, S_w, pred_thr, box_thr);
@@ -1026,7 +960,7 @@ extern "C" int vpu_roi_paste_batched(const vpu_eval_obj* objs, int32_t n, const 
         vpu_set_error("roi_paste_batched: sizes (1 <= n <= 65535)");
         return VPU_ERR_ARG;
     }
-    paste_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    rec_init_kernel<3><<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
     const int nb = vpu_grid_for(((long long)max_hw + 3) / 4, 256, 128);
     roi_paste_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, probs, S_h, S_w, pred_thr, box_thr);
     return vpu_check_launch("vpu_roi_paste_batched");
@@ -1058,7 +992,7 @@ extern "C" int vpu_annot_compose_batched(const vpu_annot_obj* objs, int32_t n, f
         vpu_set_error("annot_compose_batched: null descriptors, sizes (1 <= n <= 65535, max_hw >= 1) or a NaN threshold");
         return VPU_ERR_ARG;
     }
-    annot_init_kernel<<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    rec_init_kernel<2><<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
     const int nb = vpu_grid_for(max_hw, 1024, 128);
     annot_compose_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, thr);
     return vpu_check_launch("vpu_annot_compose_batched");
@@ -1074,7 +1008,7 @@ extern "C" int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int
         vpu_set_error("label_extract: labels not 8-byte, out not 16-byte or rec not 4-byte aligned");
         return VPU_ERR_ALIGN;
     }
-    annot_init_one_kernel<<<1, 1, 0, ST>>>(rec, H, W);
+    rec_init_one_kernel<<<1, 1, 0, ST>>>(rec, H, W);
     const int nb = vpu_grid_for(((long long)H * W + 3) / 4, 256, 1024);
     label_extract_kernel<<<(unsigned)nb, 256, 0, ST>>>(labels, out, rec, H, W, (unsigned)label);
     return vpu_check_launch("vpu_label_extract");

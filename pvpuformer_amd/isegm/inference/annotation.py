@@ -27,18 +27,17 @@ import torch
 
 from .clicker import Click, Clicker
 from .runs import KIND_LABELS, KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map, stack_objects
-from .sessions import SessionPool, n_words, pack_mask, unpack_mask
+from ._batchcore import PackedLayout, host_count_box, pack_mask, unpack_mask, upload_structs
+from .sessions import SessionPool
 
 MAX_LABEL = 65535
-_REC = 4             # int64 per record (int32 [8]: area, overwritten, rmin, rmax, cmin, cmax, 0, 0)
 
 
 # ------------------------------------------------------------------------------------------------------ host stand-ins
 def _record(mask, overwritten):
-    H, W = mask.shape
-    on = np.argwhere(mask)
-    box = [int(on[:, 0].min()), int(on[:, 0].max()), int(on[:, 1].min()), int(on[:, 1].max())] if len(on) else [H, -1, W, -1]
-    return np.array([len(on), overwritten] + box + [0, 0], dtype=np.int32)
+    """int32 [8]: area, overwritten, rmin, rmax, cmin, cmax, 0, 0."""
+    area, *box = host_count_box(mask, *mask.shape)
+    return np.array([area, overwritten] + box + [0, 0], dtype=np.int32)
 
 
 def host_annot_compose(add, total, labels, H, W, label, mode, thr):
@@ -72,14 +71,6 @@ class _Item:
         self.H, self.W, self.add, self.total, self.labels, self.label, self.mode = H, W, add, total, labels, int(label), int(mode)
 
 
-def _decode(got, items, at, masks):
-    out = []
-    for i, it in enumerate(items):
-        rec = got[_REC * i:_REC * (i + 1)].view(np.int32)
-        out.append((rec, unpack_mask(got[at[i]:at[i] + n_words(it.H * it.W)], it.H, it.W) if masks else None))
-    return out
-
-
 class DeviceAnnotOps:
     """The HIP kernels: the descriptors of a call go up in one copy, its records and packed masks come back in one."""
 
@@ -90,11 +81,8 @@ class DeviceAnnotOps:
     def compose(self, items, thr, read):
         """``read``: "masks" -> [(record, mask bool [H, W])], "records" -> [(record, None)] (one read-back each), None ->
         nothing is read back and nothing waited for."""
-        n, at, size = len(items), [], _REC * len(items)
-        for it in items:
-            at.append(size)
-            size += n_words(it.H * it.W)
-        out = torch.empty(size, device=self.device, dtype=torch.int64)
+        n, layout = len(items), PackedLayout([(it.H, it.W) for it in items])
+        out = torch.empty(layout.size, device=self.device, dtype=torch.int64)
         assert out.data_ptr() % 8 == 0
         rows = []
         for i, it in enumerate(items):
@@ -108,17 +96,16 @@ class DeviceAnnotOps:
             d.add = it.add.data_ptr() if it.add is not None else None
             d.total = it.total.data_ptr() if it.total is not None else None
             d.labels = it.labels.data_ptr() if it.labels is not None else None
-            d.bits = out.data_ptr() + 8 * at[i]
-            d.rec = out.data_ptr() + 8 * _REC * i
+            d.bits = out.data_ptr() + 8 * layout.bits_at(i)
+            d.rec = out.data_ptr() + 8 * layout.rec_at(i)
             d.H, d.W, d.label, d.mode = it.H, it.W, it.label, it.mode
             rows.append(d)
-        raw = bytes((self._lib.AnnotObj * n)(*rows))
-        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
-        self._ops.annot_compose_batched(host.to(self.device, non_blocking=True), n, thr, max(it.H * it.W for it in items))
+        host, desc, _ = upload_structs(self.device, (self._lib.AnnotObj * n)(*rows))    # (host: alive until the read-back)
+        self._ops.annot_compose_batched(desc, n, thr, max(it.H * it.W for it in items))
         if read is None:
             return None
-        got = (out if read == "masks" else out[:_REC * n]).cpu().numpy()        # the call's one synchronisation
-        return _decode(got, items, at, read == "masks")
+        got = (out if read == "masks" else out[:layout.rec_at(n)]).cpu().numpy()        # the call's one synchronisation
+        return [layout.decode(got, i, read == "masks") for i in range(n)]
 
     def extract(self, labels, label):
         """-> (fp32 [H, W] on the device, record); one read-back (32 bytes)."""

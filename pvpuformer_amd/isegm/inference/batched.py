@@ -54,6 +54,7 @@ import struct
 import numpy as np
 import torch
 
+from ._batchcore import ZoomHost, host_count_box, host_roi_paste, host_roi_resize, upload_structs
 from .clicker import Click
 from .transforms import AddHorizontalFlip, Roi, SigmoidForPred, ZoomIn, crop_resize
 
@@ -206,13 +207,9 @@ class _DeviceOps:
         return len(self._box) - 1
 
     def upload(self):
-        n = len(self._desc)
-        arr = (self._lib.EvalObj * n)(*self._desc)
-        self._box_at0 = C.sizeof(arr)                 # the box rows ride behind the descriptors in the same copy
-        raw = bytes(arr) + (bytes((self._lib.BoxRow * len(self._box))(*self._box)) if self._box else b"")
-        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
-        self._host = host                   # (kept alive until the step's read-back has synchronised)
-        self.desc = host.to(self.device, non_blocking=True)
+        # the box rows ride behind the descriptors in the same copy; _host stays alive until the step's read-back
+        self._host, self.desc, (_, self._box_at0) = upload_structs(
+            self.device, (self._lib.EvalObj * len(self._desc))(*self._desc), (self._lib.BoxRow * len(self._box))(*self._box))
 
     def _at(self, i):
         return (self.desc, i * C.sizeof(self._lib.EvalObj))
@@ -273,35 +270,21 @@ class _HostOps:
         assert self._box[first:first + len(rows)] == list(rows)
         return torch.from_numpy(_host_boxes(rows, points_nd, n_batch, size, target_size))
 
-    @staticmethod
-    def _resize(x, size):
-        if tuple(x.shape[2:]) == tuple(size):
-            return x.clone()
-        return torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=True)
-
     def resize(self, objs, first, n, size, flip, channels):
         rows = []
-        for o, (r0, r1, c0, c1), src, _, prev, _ in self._desc[first:first + n]:
-            x = torch.cat((o.image[None], o.canvas[o.prev][None, None]), 1) if prev else o.image[None]
-            rows.append((src, self._resize(x[:, :, r0:r1 + 1, c0:c1 + 1], size)))
+        for o, roi, src, _, prev, _ in self._desc[first:first + n]:
+            rows.append((src, host_roi_resize(o.image, o.canvas[o.prev] if prev else None, roi, size)))
         batch = torch.cat([r for _, r in sorted(rows, key=lambda t: t[0])], 0)
         return torch.cat([batch, batch.flip(3)], 0) if flip else batch
 
     def paste(self, objs, first, n, probs, pred_thr, box_thr):
-        for o, (r0, r1, c0, c1), src, row, _, _ in self._desc[first:first + n]:
-            patch = self._resize(probs[src:src + 1].float(), (r1 - r0 + 1, c1 - c0 + 1))
-            full = torch.zeros(o.H, o.W, dtype=torch.float32)
-            full[r0:r1 + 1, c0:c1 + 1] = patch[0, 0]
+        for o, roi, src, row, _, _ in self._desc[first:first + n]:
+            full = host_roi_paste(probs[src, 0], o.H, o.W, roi)
             o.canvas[1 - o.prev].copy_(full)
             m = full.numpy() > np.float32(pred_thr)
             o.mask.copy_(torch.from_numpy(m.astype(np.uint8)))
             g, v = o.gt.numpy() != 0, o.valid.numpy() != 0
-            stats = [int((m & g & v).sum()), int(((m | g) & v).sum())]
-            on = np.argwhere(full.numpy() > np.float32(box_thr))
-            if len(on):
-                stats += [len(on), int(on[:, 0].min()), int(on[:, 0].max()), int(on[:, 1].min()), int(on[:, 1].max())]
-            else:
-                stats += [0, o.H, -1, o.W, -1]
+            stats = [int((m & g & v).sum()), int(((m | g) & v).sum())] + host_count_box(full.numpy() > np.float32(box_thr), o.H, o.W)
             self.out[row, _STATS:] = np.array(stats + [0], dtype=np.int32).view(np.int64)
 
     def keys(self, objs, first, n):
@@ -321,72 +304,18 @@ class _HostOps:
         return self.out.copy()
 
 
-class BatchedEvaluator:
+class BatchedEvaluator(ZoomHost):
     """Runs ``evaluate_sample``'s loop (``evaluate_dataset``'s kwargs) over a stream of objects, ``batch_objects`` at a time."""
 
     def __init__(self, predictor, batch_objects, max_iou_thr, pred_thr=0.49, min_clicks=1, max_clicks=20, as_prompt_type=0):
         assert batchable(predictor, None, as_prompt_type), \
             "the predictor's transforms or the prompt type are not the batched path's (see batchable)"
         from .vpu_evaluation import prompt_schedule
-        self.pred, self.K, self.schedule = predictor, int(batch_objects), prompt_schedule(as_prompt_type)
+        super().__init__(predictor)
+        self.K, self.schedule = int(batch_objects), prompt_schedule(as_prompt_type)
         self.max_iou_thr, self.pred_thr, self.min_clicks, self.max_clicks = max_iou_thr, pred_thr, min_clicks, max_clicks
-        self.zoom = predictor.zoom_in
-        self.flip = any(type(t) is AddHorizontalFlip for t in predictor.transforms)
-        self.inv = [t for t in reversed(predictor.transforms) if type(t) is not ZoomIn]   # flip average, then sigmoid
-        self.prev_channel = bool(getattr(predictor.net, "with_prev_mask", True))
-        self.device = torch.device(predictor.device)
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
         self.keep_probs, self.final_probs = False, {}     # keep_probs: each object's last probability map (tests)
-
-    # ---------------------------------------------------------------------------------------------- ZoomIn on the host
-    def _predicted_box(self, o, clicks=()):
-        """ZoomIn._predicted_box from the read-back box of the last prediction, joined here with the positive clicks."""
-        if o.box is None:
-            return None
-        count, r0, r1, c0, c1 = o.box
-        for c in clicks:
-            if c.is_positive:
-                r, k = int(c.coords[0]), int(c.coords[1])
-                r0, r1, c0, c1 = min(r0, r), max(r1, r), min(c0, k), max(c1, k)
-        if count == 0:
-            return None
-        return Roi(r0, r1, c0, c1).grown(self.zoom.expansion_ratio, self.zoom.min_crop_size).clipped(o.H, o.W)
-
-    def _plan(self, o):
-        """ZoomIn.transform of this click: (input roi, network input size, clicks in network coordinates, paste roi)."""
-        whole, clicks, zi = Roi.whole(o.H, o.W), o.clicks, self.zoom
-        crop = False
-        if zi is not None and len(clicks) > zi.skip_clicks:
-            box = self._predicted_box(o, clicks)
-            if box is None and zi.skip_clicks < 0:
-                box = whole                             # zoom from the very first click on
-            if box is not None:
-                held = o.roi
-                if held is None or not Roi(*held).encloses(clicks) or box.overlap(held) < zi.recompute_thresh_iou:
-                    o.roi = box
-                crop = True
-        if crop:
-            roi = Roi(*o.roi)
-            size = tuple(int(s) for s in roi.output_size(zi.target_size))
-            net_clicks = [c.copy(coords=roi.to_crop(c.coords, size)) for c in clicks]
-            return roi, size, net_clicks, roi
-        return whole, (o.H, o.W), list(clicks), (Roi(*o.roi) if o.roi is not None else whole)
-
-    def _own_rows(self, clicks):
-        """Rows per polarity of ``get_points_nd([clicks])``: the click layout the sequential call sees for this object."""
-        pos = sum(c.is_positive for c in clicks)
-        n = max(pos, len(clicks) - pos)
-        if self.pred.net_clicks_limit is not None:
-            n = min(self.pred.net_clicks_limit, n)
-        return max(1, n)
-
-    def _wants_recalc(self, o):
-        """ZoomIn.check_possible_recalculation after this step's prediction (o.box is its box)."""
-        zi = self.zoom
-        if zi is None or o.roi is not None or zi.skip_clicks > 0:
-            return False
-        box = self._predicted_box(o)
-        return box is not None and box.overlap(Roi.whole(o.H, o.W)) < 0.50
 
     # ---------------------------------------------------------------------------------------------- the loop
     def run(self, objects):
@@ -503,10 +432,7 @@ class BatchedEvaluator:
         flag_of, n_box = {}, 0
         for size, members, first, pfirst, box_batches in spans:
             image_nd = ops.resize(members, first, len(members), size, self.flip, 4 if self.prev_channel else 3)
-            lists = [o.plan[2] for o in members]
-            if self.flip:
-                lists = lists + [[c.copy(coords=(c.coords[0], size[1] - c.coords[1] - 1)) for c in cl] for cl in lists]
-            points_nd = self.pred.get_points_nd(lists).float()
+            points_nd = self.pred.get_points_nd(self.flipped_click_lists([o.plan[2] for o in members], size[1])).float()
             boxes, kind = None, 0
             for box_size, host_box, js, bfirst, brows in box_batches:
                 n_batch, target = points_nd.shape[1] // 2, (self.zoom.target_size if self.zoom else None)
@@ -529,13 +455,7 @@ class BatchedEvaluator:
                         boxes[:, 4] = -1
                     boxes[at] = got.to(self.device)
                 kind = 1
-            logits = self.pred.net(image_nd, points_nd, (points_nd, boxes, None), kind)['instances']
-            if tuple(logits.shape[2:]) != tuple(image_nd.shape[2:]):
-                from .transforms import resize_align_corners
-                logits = resize_align_corners(logits, image_nd.shape[2:])
-            probs = logits
-            for t in self.inv:
-                probs = t.inv_transform(probs)
+            probs = self._forward(image_nd, points_nd, (points_nd, boxes, None), kind)
             ops.paste(members, pfirst, len(members), probs, self.pred_thr, self.zoom.prob_thresh if self.zoom else 0.5)
         if key_objs:
             ops.keys(key_objs, kfirst, len(key_objs))

@@ -20,6 +20,8 @@ import ctypes
 import numpy as np
 import torch
 
+from ._batchcore import upload_structs
+
 KIND_PROB, KIND_LABELS = 0, 1     # vpu_runs_obj.kind: fp32 map > thr (values 0 / 1), 16-bit label map
 #                                 # vpu_unrun_obj.kind: fp32 map of value == label, 16-bit label map
 
@@ -220,9 +222,7 @@ class DeviceRunOps:
             d = self._lib.RunsObj()
             d.src, d.H, d.W, d.kind, d.thr = tensor.data_ptr(), tensor.shape[0], tensor.shape[1], kind, float(thr)
             rows.append(d)
-        raw = bytes((self._lib.RunsObj * n)(*rows))
-        host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()       # (alive until the last read-back)
-        desc = host.to(self.device, non_blocking=True)
+        host, desc, _ = upload_structs(self.device, (self._lib.RunsObj * n)(*rows))    # (host: alive until the last read-back)
         sizes = [tuple(t.shape) for t, _, _ in items]
         scratch = torch.empty(self._ops.runs_scratch_len(sizes), device=self.device, dtype=torch.int32)
         header = torch.empty(n + 1, device=self.device, dtype=torch.int32)

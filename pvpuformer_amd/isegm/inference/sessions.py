@@ -9,9 +9,9 @@ and the ZoomIn box, and ONE device-to-host copy of the records and packed masks 
 per session).  The probability maps stay on the device (``probs``).
 
 Per session the results are those of a private copy of the predictor: every per-session operation is the sequential one
-(``ZoomIn.transform`` restated on the host exactly as ``BatchedEvaluator._plan`` does, the crop / resize / mirror of
+(``ZoomIn.transform`` on the host by ``ZoomHost``, which ``BatchedEvaluator`` runs on too, the crop / resize / mirror of
 ``vpu_roi_resize_batched``, the predictor's own flip average and sigmoid on the whole batch, the paste with
-``vpu_roi_paste_batched``'s per-pixel expression); what the batch shares is the network, whose click rows are padded to a
+``vpu_roi_paste_batched``'s per-pixel function); what the batch shares is the network, whose click rows are padded to a
 common count by ``get_points_nd`` with not-a-point rows that it ignores.  In the ``f32`` engine mode the maps are the
 sequential ones bit for bit.  ``check_possible_recalculation`` is honoured inside the call: the sessions it fires for run a
 second forward of their own, as ``get_prediction`` re-runs itself.
@@ -34,50 +34,19 @@ import numpy as np
 import torch
 
 from ..model.scribble import scribble_profiles
-from .batched import BatchedEvaluator, _load_image, _padded_slot, batchable
+from ._batchcore import (PackedLayout, ZoomHost, host_count_box, host_roi_paste, host_roi_resize, n_words, pack_mask,  # noqa: F401
+                         unpack_mask, upload_structs)
+from .batched import _load_image, _padded_slot, batchable
 from .runs import KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map
-from .transforms import AddHorizontalFlip, Roi, ZoomIn
-
-_REC = 4             # int64 per session record (int32 [8]: area, count, rmin, rmax, cmin, cmax, 0, 0)
-
-
-# ------------------------------------------------------------------------------------------------------ the bit codec
-def n_words(hw):
-    return (int(hw) + 63) // 64
-
-
-def pack_mask(mask):
-    """bool [H, W] -> uint64 [ceil(H * W / 64)]: pixel i = r * W + c is bit i & 63 of little-endian word i >> 6; the bits at or
-    beyond H * W are zero."""
-    flat = np.ascontiguousarray(mask, dtype=bool).reshape(-1)
-    padded = np.zeros(n_words(flat.size) * 64, dtype=bool)
-    padded[:flat.size] = flat
-    return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
-
-
-def unpack_mask(words, H, W):
-    """The inverse of ``pack_mask``: 64-bit words (uint64 or the int64 of a read-back) -> bool [H, W]."""
-    raw = np.ascontiguousarray(words).view(np.uint64).astype("<u8").view(np.uint8)
-    return np.unpackbits(raw, bitorder="little")[:H * W].astype(bool).reshape(H, W)
 
 
 def host_session_paste(prob_map, H, W, roi, pred_thr, box_thr):
     """Stand-in of vpu_session_paste_batched for one session: ``prob_map`` fp32 [S_h, S_w] (cpu) resized to the roi and pasted
-    into zeros -> (canvas fp32 [H, W], packed mask uint64, record int32 [8])."""
-    r0, r1, c0, c1 = roi
-    h, w = r1 - r0 + 1, c1 - c0 + 1
-    patch = prob_map.float()[None, None]
-    if tuple(patch.shape[2:]) != (h, w):
-        patch = torch.nn.functional.interpolate(patch, size=(h, w), mode="bilinear", align_corners=True)
-    canvas = torch.zeros(H, W, dtype=torch.float32)
-    canvas[r0:r1 + 1, c0:c1 + 1] = patch[0, 0]
+    into zeros -> (canvas fp32 [H, W], packed mask uint64, record int32 [8]: area, count, rmin, rmax, cmin, cmax, 0, 0)."""
+    canvas = host_roi_paste(prob_map, H, W, roi)
     values = canvas.numpy()
     mask = values > np.float32(pred_thr)
-    on = np.argwhere(values > np.float32(box_thr))
-    if len(on):
-        box = [len(on), int(on[:, 0].min()), int(on[:, 0].max()), int(on[:, 1].min()), int(on[:, 1].max())]
-    else:
-        box = [0, H, -1, W, -1]
+    box = host_count_box(values > np.float32(box_thr), H, W)
     return canvas, pack_mask(mask), np.array([int(mask.sum())] + box + [0, 0], dtype=np.int32)
 
 
@@ -124,7 +93,7 @@ def stroke_row(xy, img, rng):
 
 
 class _Session:
-    """One session's state (a slot of the pool); the attribute names are the ones ``BatchedEvaluator._plan`` reads."""
+    """One session's state (a slot of the pool, as ``ZoomHost`` reads one)."""
 
     def __init__(self, sid, image, seed=None):
         self.sid, self.image = sid, image
@@ -139,22 +108,14 @@ class _Session:
         self.drawn = None              # the drawn prompt of the call in progress: ("box", [2, 2]) / ("stroke", [P, 2]) of (row, col)
 
 
-class _Round:
-    """Layout of a forward round's read-back: ``_REC`` int64 per session, then every session's packed words."""
+class _Round(PackedLayout):
+    """Layout of a forward round's read-back, keyed by session id: ``row[sid]`` is the session's row, ``at[sid]`` the int64
+    offset of its packed words."""
 
     def __init__(self, sessions):
+        super().__init__([(s.H, s.W) for s in sessions])
         self.row = {s.sid: i for i, s in enumerate(sessions)}
-        self.at, at = {}, _REC * len(sessions)
-        for s in sessions:
-            self.at[s.sid] = at
-            at += n_words(s.H * s.W)
-        self.size = at
-
-    def decode(self, out, s):
-        """(record int32 [8], mask bool [H, W]) of session ``s`` from the read-back ``out`` (int64)."""
-        i = self.row[s.sid]
-        rec = out[_REC * i:_REC * (i + 1)].view(np.int32)
-        return rec, unpack_mask(out[self.at[s.sid]:self.at[s.sid] + n_words(s.H * s.W)], s.H, s.W)
+        self.at = {s.sid: self.bits_at(i) for i, s in enumerate(sessions)}
 
 
 class _DeviceOps:
@@ -190,7 +151,7 @@ class _DeviceOps:
         d = self._lib.SessionObj()
         d.canvas = canvas.data_ptr()
         d.bits = self.out.data_ptr() + 8 * self.layout.at[s.sid]
-        d.rec = self.out.data_ptr() + 8 * _REC * self.layout.row[s.sid]
+        d.rec = self.out.data_ptr() + 8 * self.layout.rec_at(self.layout.row[s.sid])
         d.H, d.W = s.H, s.W
         d.r0, d.r1, d.c0, d.c1 = r0, r1, c0, c1
         d.src = src
@@ -198,11 +159,9 @@ class _DeviceOps:
         return len(self._out) - 1
 
     def upload(self):
-        inp = (self._lib.EvalObj * len(self._inp))(*self._inp)
-        self._out_at0 = C.sizeof(inp)                 # the paste rows ride behind the input rows in the same copy
-        raw = bytes(inp) + bytes((self._lib.SessionObj * len(self._out))(*self._out))
-        self._host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()   # (alive until the read-back)
-        self.desc = self._host.to(self.device, non_blocking=True)
+        # the paste rows ride behind the input rows in the same copy; _host stays alive until the read-back
+        self._host, self.desc, (_, self._out_at0) = upload_structs(
+            self.device, (self._lib.EvalObj * len(self._inp))(*self._inp), (self._lib.SessionObj * len(self._out))(*self._out))
 
     def resize(self, sessions, first, size, flip, channels):
         n = len(sessions)
@@ -243,12 +202,8 @@ class _HostOps:
 
     def resize(self, sessions, first, size, flip, channels):
         rows = []
-        for s, (r0, r1, c0, c1), src, prev in self._inp[first:first + len(sessions)]:
-            x = torch.cat((s.image[None], prev[None, None]), 1) if channels == 4 else s.image[None]
-            x = x[:, :, r0:r1 + 1, c0:c1 + 1]
-            if tuple(x.shape[2:]) != tuple(size):
-                x = torch.nn.functional.interpolate(x, size=tuple(size), mode="bilinear", align_corners=True)
-            rows.append((src, x.clone()))
+        for s, roi, src, prev in self._inp[first:first + len(sessions)]:
+            rows.append((src, host_roi_resize(s.image, prev if channels == 4 else None, roi, size)))
         batch = torch.cat([r for _, r in sorted(rows, key=lambda t: t[0])], 0)
         return torch.cat([batch, batch.flip(3)], 0) if flip else batch
 
@@ -256,15 +211,13 @@ class _HostOps:
         for s, roi, src in self._out[first:first + len(sessions)]:
             canvas, words, rec = host_session_paste(probs[src, 0], s.H, s.W, roi, pred_thr, box_thr)
             s.canvas[1 - s.prev].copy_(canvas)
-            i, at = self.layout.row[s.sid], self.layout.at[s.sid]
-            self.out[_REC * i:_REC * (i + 1)] = rec.view(np.int64)
-            self.out[at:at + len(words)] = words.view(np.int64)
+            self.layout.put(self.out, self.layout.row[s.sid], rec, words)
 
     def readback(self):
         return self.out.copy()
 
 
-class SessionPool:
+class SessionPool(ZoomHost):
     """``pool = SessionPool(predictor, max_sessions=8, pred_thr=0.49)``; ``predictor``: a ``BasePredictor`` for which
     ``batched.batchable(predictor)`` holds (ValueError otherwise).  It lends the pool its network, its transforms' parameters,
     ``get_points_nd`` / ``net_clicks_limit`` and the cascade rule for ``prev_masks``; its own image and state are not touched.
@@ -277,29 +230,18 @@ class SessionPool:
     ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``).  ``ops_runs``
     holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``."""
 
-    # ZoomIn on the host, from the box read back with the last prediction: BatchedEvaluator's restatement of ZoomIn.transform /
-    # _predicted_box / check_possible_recalculation, used as it stands (they read .zoom and a slot's clicks / roi / box / H / W)
-    _predicted_box = BatchedEvaluator._predicted_box
-    _plan = BatchedEvaluator._plan
-    _wants_recalc = BatchedEvaluator._wants_recalc
-    _own_rows = BatchedEvaluator._own_rows
-
     def __init__(self, predictor, max_sessions=8, pred_thr=0.49, max_batch=None, max_stroke_points=1024):
         if not batchable(predictor):
             raise ValueError("SessionPool: the predictor's transforms are not the batched path's (batched.batchable): only "
                              "[ZoomIn with a (height, width) target_size] [SigmoidForPred] [AddHorizontalFlip]")
         if int(max_sessions) < 1 or (max_batch is not None and int(max_batch) < 1):
             raise ValueError("SessionPool: max_sessions and max_batch must be at least 1")
-        self.pred, self.max_sessions, self.pred_thr = predictor, int(max_sessions), float(pred_thr)
+        super().__init__(predictor)
+        self.max_sessions, self.pred_thr = int(max_sessions), float(pred_thr)
         self.max_batch = int(max_batch) if max_batch is not None else self.max_sessions
         self.max_stroke_points = int(max_stroke_points)
-        self.zoom = predictor.zoom_in
-        self.flip = any(type(t) is AddHorizontalFlip for t in predictor.transforms)
-        self.inv = [t for t in reversed(predictor.transforms) if type(t) is not ZoomIn]   # flip average, then sigmoid
-        self.prev_channel = bool(getattr(predictor.net, "with_prev_mask", True))
         size = getattr(predictor.net, "image_size", None)     # the length of the stroke profiles (the model's own image size)
         self.prompt_img = int(size[0]) if size is not None else None
-        self.device = torch.device(predictor.device)
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
         self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
         self._slots = [None] * self.max_sessions
@@ -506,28 +448,15 @@ class SessionPool:
         ops.upload()
         for size, members, first, pfirst in spans:
             image_nd = ops.resize(members, first, size, self.flip, 4 if self.prev_channel else 3)
-            lists = [s.plan[2] for s in members]
-            if self.flip:
-                lists = lists + [[c.copy(coords=(c.coords[0], size[1] - c.coords[1] - 1)) for c in cl] for cl in lists]
-            points_nd = self.pred.get_points_nd(lists).float()
-            prompts, ptype = self._prompts(members, size, points_nd)
-            if ptype == 0:
-                logits = self.pred.net(image_nd, points_nd)['instances']
-            else:
-                logits = self.pred.net(image_nd, points_nd, prompts, ptype)['instances']
+            points_nd = self.pred.get_points_nd(self.flipped_click_lists([s.plan[2] for s in members], size[1])).float()
+            probs = self._forward(image_nd, points_nd, *self._prompts(members, size, points_nd))
             self.forwards += 1
-            if tuple(logits.shape[2:]) != tuple(image_nd.shape[2:]):
-                from .transforms import resize_align_corners
-                logits = resize_align_corners(logits, image_nd.shape[2:])
-            probs = logits
-            for t in self.inv:
-                probs = t.inv_transform(probs)
             ops.paste(members, pfirst, probs, self.pred_thr, self.zoom.prob_thresh if self.zoom else 0.5)
         got = ops.readback()
         self.readbacks += 1
         again = []
         for s in todo:
-            rec, mask = ops.layout.decode(got, s)
+            rec, mask = ops.layout.decode(got, ops.layout.row[s.sid])
             if self.zoom is not None:
                 s.box = tuple(int(v) for v in rec[1:6])       # ZoomIn._probs is the new prediction either way
             if self._wants_recalc(s):

@@ -215,3 +215,42 @@ def test_bit_codec_round_trip(shape):
     one.reshape(-1)[H * W - 1] = True
     w = sessions.pack_mask(one)
     assert int(w[(H * W - 1) >> 6]) == 1 << ((H * W - 1) & 63) and int(w.astype(object).sum()) == int(w[-1])
+
+
+def test_packed_layout_round_trip_and_count_box():
+    """``PackedLayout`` and ``host_count_box`` at H * W in {1, 63, 64, 65, 4290}, one buffer for all rows: every row's record
+    and mask come back as they went in, no row writes into a neighbour, and the record of an empty mask is {0, H, -1, W, -1}."""
+    from pvpuformer_amd.isegm.inference._batchcore import _REC, PackedLayout, host_count_box
+    shapes = [(1, 1), (7, 9), (8, 8), (5, 13), (66, 65)]
+    assert [H * W for H, W in shapes] == [1, 63, 64, 65, 4290]
+    sizes = shapes + shapes                                  # each shape once with a random mask, once with an empty one
+    layout = PackedLayout(sizes)
+    words = [sessions.n_words(H * W) for H, W in sizes]
+    assert layout.size == _REC * len(sizes) + sum(words)
+    assert [layout.rec_at(i) for i in range(len(sizes))] == [4 * i for i in range(len(sizes))]
+    assert [layout.bits_at(i) for i in range(len(sizes))] == [4 * len(sizes) + sum(words[:i]) for i in range(len(sizes))]
+    out = np.full(layout.size, -1, dtype=np.int64)
+    masks, recs = [], []
+    for i, (H, W) in enumerate(sizes):
+        mask = np.random.RandomState(i).rand(H, W) < 0.5 if i < len(shapes) else np.zeros((H, W), bool)
+        mask[-1, -1] = i < len(shapes)                       # the last pixel: the bit next to the padding
+        box = host_count_box(mask, H, W)
+        if i >= len(shapes):
+            assert box == [0, H, -1, W, -1]
+        else:
+            rows, cols = np.nonzero(mask)
+            assert box == [int(mask.sum()), rows.min(), rows.max(), cols.min(), cols.max()]
+        rec = np.array([i] + box + [0, 0], dtype=np.int32)
+        layout.put(out, i, rec, sessions.pack_mask(mask))
+        masks.append(mask)
+        recs.append(rec)
+    assert not (out == -1).any() and (out[:_REC * len(sizes)].view(np.int32).reshape(-1, 8)[:, 6:] == 0).all()
+    for i in range(len(sizes)):                             # after every row is written: nothing was clobbered
+        rec, mask = layout.decode(out, i)
+        assert rec.tolist() == recs[i].tolist() and mask.dtype == bool and np.array_equal(mask, masks[i])
+        rec, none = layout.decode(out, i, masks=False)
+        assert rec.tolist() == recs[i].tolist() and none is None
+    # the sessions' layout is this one keyed by session id
+    rnd = sessions._Round([type("S", (), dict(sid=10 + i, H=H, W=W)) for i, (H, W) in enumerate(sizes)])
+    assert rnd.size == layout.size and [rnd.at[10 + i] for i in range(len(sizes))] == [layout.bits_at(i) for i in range(len(sizes))]
+    assert np.array_equal(rnd.decode(out, rnd.row[13])[1], masks[3])
