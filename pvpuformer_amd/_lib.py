@@ -90,6 +90,14 @@ class UnrunObj(C.Structure):
                 ("kind", C.c_int32), ("label", C.c_int32), ("pad", C.c_int32)]
 
 
+class TidyObj(C.Structure):
+    """vpu_tidy_obj (include/vpu_hip.h): one map of vpu_regions_tidy_batched."""
+    _fields_ = [("add", C.c_void_p), ("total", C.c_void_p), ("add_out", C.c_void_p), ("total_out", C.c_void_p),
+                ("bits", C.c_void_p), ("rec", C.c_void_p), ("seeds", C.c_void_p), ("scratch", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("n_seeds", C.c_int32), ("min_area", C.c_int32), ("max_hole", C.c_int32),
+                ("keep", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32)]
+
+
 SIGNATURES = {
     "vpu_gemm": [C.POINTER(GemmDesc), _P],
     "vpu_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _I, _P],
@@ -144,6 +152,7 @@ SIGNATURES = {
     "vpu_runs_count_batched": [_P, _P, _I, _P, _L, _P, _P],
     "vpu_runs_write_batched": [_P, _P, _I, _P, _L, _P, _I, _P],
     "vpu_runs_decode_batched": [_P, _P, _I, _P],
+    "vpu_regions_tidy_batched": [_P, _P, _I, _F, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -6,6 +6,7 @@
 #include <cstdio>
 
 #include "vpu_common.h"
+#include "cc_union.h"
 #include "interp_ac.h"
 #include "../../include/vpu_hip.h"
 
@@ -33,6 +34,7 @@ struct MaskRec {
 using PasteRec = MaskRec<3, 2>;
 using SessionRec = MaskRec<2, 1>;
 using AnnotRec = MaskRec<2, 0>;
+using TidyRec = MaskRec<3, 0>;
 
 template <int NSUM>
 __device__ __forceinline__ void rec_init(int* rec, int H, int W) {
@@ -44,6 +46,7 @@ __device__ __forceinline__ void rec_init(int* rec, int H, int W) {
 __device__ __forceinline__ int* rec_of(const vpu_eval_obj& d) { return reinterpret_cast<int*>(d.out + 2); }
 __device__ __forceinline__ int* rec_of(const vpu_session_obj& d) { return d.rec; }
 __device__ __forceinline__ int* rec_of(const vpu_annot_obj& d) { return d.rec; }
+__device__ __forceinline__ int* rec_of(const vpu_tidy_obj& d) { return d.rec; }
 
 template <int NSUM, class D>
 __global__ void rec_init_kernel(const D* __restrict__ objs, int n) {
@@ -125,6 +128,17 @@ __device__ __forceinline__ void load4(const uint16_t* p, int64_t i0, int64_t HW,
     if (i0 + 3 < HW) {
         const uint2 q = *reinterpret_cast<const uint2*>(p + i0);
         v[0] = q.x & 0xffffu; v[1] = q.x >> 16; v[2] = q.y & 0xffffu; v[3] = q.y >> 16;
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (i0 + u < HW) v[u] = p[i0 + u];
+    }
+}
+
+__device__ __forceinline__ void load4(const int* p, int64_t i0, int64_t HW, int (&v)[4]) {
+    if (i0 + 3 < HW) {
+        const int4 q = *reinterpret_cast<const int4*>(p + i0);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
     } else {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -616,7 +630,8 @@ __global__ __launch_bounds__(256) void crops_blend_kernel(const float* __restric
 //     so the pixels whose bit is clear are written back as they were read.
 
 // the mask pixel (r, c) u places after the quad's first pixel (r0, c0): a quad may span several rows when W < 4
-__device__ __forceinline__ void annot_count(AnnotRec& a, int r, int c, int W) {
+template <class Rec>
+__device__ __forceinline__ void annot_count(Rec& a, int r, int c, int W) {
     while (c >= W) { c -= W; ++r; }
     a.count(r, c);
 }
@@ -861,6 +876,236 @@ __global__ __launch_bounds__(VPU_RUNS_COLS) void unrun_walk_kernel(const vpu_unr
     else unrun_walk<1>(d, c, r0, r1);
 }
 
+// -------------------------------------------------------------------------------------------------------------------
+// (9) region clean-up (isegm/inference/regions.py, rules T1-T8 of include/vpu_hip.h): islands dropped, holes filled, on n
+//     maps of different sizes, with no table of components.  Per item the scratch holds a 4-int header (the packed key of the
+//     largest component), lab [HW] (the union-find parents: first of the foreground of M, 8-connected, then -- rewritten in
+//     place -- of the background of M1, 4-connected, and last of the result M2, 8-connected; -1 off the labelled set), accA [HW] and accB [HW]: area in bits 0 .. 30
+//     and one flag in bit 31 (A: holds a positive seed; B: touches the border or holds a negative seed) of the component whose
+//     root is that pixel.  Every labelling kernel gives lane l of a wave pixel (block * 256 + thread) of the flat map, so a wave
+//     is 64 consecutive pixels at a multiple of 64.  Kernel boundaries order the passes; inside a pass pixels talk only
+//     through agent-scope integer atomics (cc_union.h, atomicAdd / Or / Max), which makes the result independent of their order.
+constexpr int TIDY_FLAG = (int)0x80000000;
+
+struct TidyItem {
+    int64_t HW;
+    int *hdr, *lab, *accA, *accB;
+    __device__ __forceinline__ explicit TidyItem(const vpu_tidy_obj& d) : HW((int64_t)d.H * d.W), hdr(d.scratch), lab(d.scratch + 4),
+                                                                         accA(d.scratch + 4 + HW), accB(d.scratch + 4 + 2 * HW) {}
+};
+
+//     The first pixel of the horizontal run of lane's pixel inside its wave (-1 off the set): a run starts where the lane
+//     below is off the set, at lane 0 and at column 0.  The pieces of a run that spans waves are joined by tidy_merge_kernel.
+//     All 64 lanes must call it.
+__device__ __forceinline__ int tidy_run_start(bool member, bool row_start, int i, int lane) {
+    const unsigned long long on = __builtin_amdgcn_ballot_w64(member), rs = __builtin_amdgcn_ballot_w64(row_start);
+    const unsigned long long starts = on & (~(on << 1) | rs | 1ull);
+    if (!member) return -1;
+    const unsigned long long below = starts & ((2ull << lane) - 1ull);      // (not empty: the run's lowest lane is a start)
+    return i - (lane - (63 - __builtin_clzll(below)));
+}
+
+//     acc[r] += 1 (OR false) or acc[r] |= TIDY_FLAG (OR true) for the lanes that are on: one atomic per wave when they all have
+//     the same root (Guideline 12; the common case, a wave inside one region), one per lane otherwise.  All 64 lanes must call it.
+template <bool OR>
+__device__ __forceinline__ void tidy_wave_acc(int* __restrict__ acc, int r, bool on, int lane) {
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(on);
+    if (mask == 0) return;
+    const int first = __builtin_ctzll(mask), r0 = __shfl(r, first, 64);
+    const bool uniform = __builtin_amdgcn_ballot_w64(on && r != r0) == 0;
+    if (uniform) {
+        if (lane == first) {
+            if (OR) atomicOr(acc + r0, TIDY_FLAG);
+            else atomicAdd(acc + r0, __builtin_popcountll(mask));
+        }
+    } else if (on) {
+        if (OR) atomicOr(acc + r, TIDY_FLAG);
+        else atomicAdd(acc + r, 1);
+    }
+}
+
+#define TIDY_PIXEL                                                                        \
+    const vpu_tidy_obj& d = objs[blockIdx.y];                                             \
+    const TidyItem s(d);                                                                  \
+    if ((int64_t)blockIdx.x * 256 >= s.HW) return;                                        \
+    const int64_t i64 = (int64_t)blockIdx.x * 256 + threadIdx.x;                          \
+    const bool in = i64 < s.HW;                                                           \
+    const int i = (int)i64, lane = threadIdx.x & 63
+
+//     M = max(total, add) > thr: the run starts of its foreground, both accumulators and the header cleared
+__global__ __launch_bounds__(256) void tidy_init_kernel(const vpu_tidy_obj* __restrict__ objs, float thr) {
+    TIDY_PIXEL;
+    bool fg = false;
+    if (in) {
+        const float t = d.total ? d.total[i] : 0.f, a = d.add ? d.add[i] : 0.f;
+        fg = fmaxf(t, a) > thr;
+        s.accA[i] = 0;
+        s.accB[i] = 0;
+    }
+    const int v = tidy_run_start(fg, in && i % d.W == 0, i, lane);
+    if (in) s.lab[i] = v;
+    if (i64 < 4) s.hdr[i] = 0;
+}
+
+//     Runs of adjacent rows joined: N / NW / NE for the 8-connected foreground (cc_merge_kernel's rule: a run of the row above
+//     is joined once per run of this row), N only for the 4-connected background; and W at lane 0, where tidy_run_start cut.
+//     Membership is lab >= 0, which no union changes.
+template <bool CONN8>
+__global__ __launch_bounds__(256) void tidy_merge_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    TIDY_PIXEL;
+    int* lab = s.lab;
+    if (!in || lab[i] < 0) return;
+    const int W = d.W, r = i / W, c = i - r * W;
+    const bool left = c > 0 && lab[i - 1] >= 0;
+    if (left && lane == 0) cc_union(lab, i, i - 1);
+    if (r == 0) return;
+    const bool n = lab[i - W] >= 0, nw = c > 0 && lab[i - W - 1] >= 0;
+    if (n && !(left && nw)) cc_union(lab, i, i - W);
+    if (CONN8) {
+        if (!n && nw && !left) cc_union(lab, i, i - W - 1);
+        if (!n && c + 1 < W && lab[i - W + 1] >= 0) cc_union(lab, i, i - W + 1);
+    }
+}
+
+//     lab = the root; the area of every component summed at its root; PHASE 1 (background): the flag of every component that
+//     holds a pixel of the first or last row or column
+template <int PHASE>
+__global__ __launch_bounds__(256) void tidy_flatten_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    TIDY_PIXEL;
+    int* lab = s.lab;
+    const bool on = in && lab[i] >= 0;
+    int root = -1;
+    if (on) {
+        // a read-only walk (the unions are complete): cc_find's path halving would re-point OTHER pixels to a grandparent and
+        // could so overwrite the root their own thread has just stored; a walk that meets such a stored root is simply done
+        root = i;
+        while (true) {
+            const int p = __hip_atomic_load(lab + root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (p == root) break;
+            root = p;
+        }
+        __hip_atomic_store(lab + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    int* acc = PHASE == 0 ? s.accA : s.accB;
+    tidy_wave_acc<false>(acc, root, on, lane);
+    if (PHASE == 1) {
+        const int r = i / d.W, c = i - r * d.W;
+        tidy_wave_acc<true>(acc, root, on && (r == 0 || r == d.H - 1 || c == 0 || c == d.W - 1), lane);
+    }
+}
+
+//     the flag of the components that hold a seed: PHASE 0 the positive ones on the foreground, PHASE 1 the negative ones on the
+//     background; one block per item
+template <int PHASE>
+__global__ __launch_bounds__(256) void tidy_seed_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    const vpu_tidy_obj& d = objs[blockIdx.x];
+    const TidyItem s(d);
+    int* acc = PHASE == 0 ? s.accA : s.accB;
+    for (int k = threadIdx.x; k < d.n_seeds; k += 256) {
+        const int r = d.seeds[3 * k], c = d.seeds[3 * k + 1];
+        const bool positive = d.seeds[3 * k + 2] != 0;
+        if (r < 0 || r >= d.H || c < 0 || c >= d.W || positive != (PHASE == 0)) continue;
+        const int root = s.lab[(int64_t)r * d.W + c];
+        if (root >= 0) atomicOr(acc + root, TIDY_FLAG);
+    }
+}
+
+//     hdr[0 .. 1] = the largest (area, ~root) of the foreground components, vpu_masked_argmax's packing: the greatest area, of equal
+//     ones the smallest root; the wave's maximum first, then one atomic per wave
+__global__ __launch_bounds__(256) void tidy_largest_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    TIDY_PIXEL;
+    if (d.keep != VPU_TIDY_LARGEST) return;
+    unsigned long long key = 0;
+    if (in && s.lab[i] == i) key = ((unsigned long long)(unsigned)(s.accA[i] & ~TIDY_FLAG) << 32) | (unsigned)~i;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, 64);
+        key = other > key ? other : key;
+    }
+    if (lane == 0 && key) atomicMax(reinterpret_cast<unsigned long long*>(s.hdr), key);
+}
+
+//     T2-T4: a pixel is in M1 when its component is kept.  Then lab is rewritten in place -- a thread reads and writes its own
+//     entry only -- as the run starts of the background of M1 (-1 on M1).
+__global__ __launch_bounds__(256) void tidy_keep_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    TIDY_PIXEL;
+    bool kept = false;
+    if (in && s.lab[i] >= 0) {
+        const int root = s.lab[i], a = s.accA[root], area = a & ~TIDY_FLAG;
+        kept = a < 0;                                                            // T2: protected by a positive seed
+        if (d.keep == VPU_TIDY_ALL) kept = kept || area >= d.min_area;
+        if (d.keep == VPU_TIDY_LARGEST) {
+            const unsigned long long best = *reinterpret_cast<const unsigned long long*>(s.hdr);
+            kept = kept || (best != 0 && (unsigned)root == ~(unsigned)best);
+        }
+    }
+    const int v = tidy_run_start(in && !kept, in && i % d.W == 0, i, lane);
+    if (in) s.lab[i] = v;
+}
+
+//     T5-T6: lab < 0 is M1; else accB at the pixel's root says whether its background region is a hole that is filled.  lab is
+//     rewritten in place once more, as the run starts of M2 (-1 off it): tidy_merge_kernel<true> then labels the result, whose
+//     roots are its components (a filled hole joins the ring around it with a kept island inside it).
+__global__ __launch_bounds__(256) void tidy_fill_kernel(const vpu_tidy_obj* __restrict__ objs) {
+    TIDY_PIXEL;
+    bool m2 = false;
+    if (in) {
+        const int root = s.lab[i];
+        m2 = root < 0;
+        if (!m2 && d.max_hole > 0) {
+            const int hole = s.accB[root];                    // (negative: the region is no hole, or holds a negative seed)
+            m2 = hole >= 0 && hole <= d.max_hole;
+        }
+    }
+    const int v = tidy_run_start(m2, in && i % d.W == 0, i, lane);
+    if (in) s.lab[i] = v;
+}
+
+//     T7-T8 in annot_compose_kernel's quad pattern.  lab >= 0 is M2, and a pixel that is its own parent is the root of one of
+//     its components: they are counted into rec[7], the wave's sum first.  The maps are copied with the two edits, M2 packed
+//     and counted.
+__global__ __launch_bounds__(256) void tidy_apply_kernel(const vpu_tidy_obj* __restrict__ objs, float thr) {
+    const vpu_tidy_obj& d = objs[blockIdx.y];
+    const TidyItem s(d);
+    const int64_t HW = s.HW, words = (HW + 63) >> 6, turns = (HW + 255) >> 8;
+    const int lane = threadIdx.x & 63;
+    TidyRec a;
+    int roots = 0;
+    for (int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); k < turns; k += (int64_t)gridDim.x * 4) {
+        const int64_t i0 = (k << 8) + 4 * lane;
+        float t[4] = {0.f, 0.f, 0.f, 0.f}, ad[4] = {0.f, 0.f, 0.f, 0.f};
+        int lb[4] = {-1, -1, -1, -1};
+        if (d.total) load4(d.total, i0, HW, t);
+        if (d.add) load4(d.add, i0, HW, ad);
+        load4(s.lab, i0, HW, lb);
+        unsigned nib = 0;
+        if (i0 < HW) {
+            const int r0 = (int)(i0 / d.W), c0 = (int)(i0 - (int64_t)r0 * d.W);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (i0 + u < HW) {
+                    const bool m = fmaxf(t[u], ad[u]) > thr;
+                    const bool m2 = lb[u] >= 0;
+                    if (lb[u] == (int)(i0 + u)) ++roots;
+                    if (m2) {
+                        nib |= 1u << u;
+                        annot_count(a, r0, c0 + u, d.W);
+                    }
+                    if (m && !m2) { ++a.sum[1]; t[u] = 0.f; ad[u] = 0.f; }
+                    if (m2 && !m) { ++a.sum[2]; t[u] = 1.f; ad[u] = 1.f; }
+                }
+            }
+        }
+        if (d.total_out) store4(d.total_out, i0, HW, t);
+        if (d.add_out) store4(d.add_out, i0, HW, ad);
+        quad_word_store(d.bits, k, lane, nib, words);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) roots += __shfl_xor(roots, o, 64);
+    if (lane == 0 && roots) atomicAdd(d.rec + 7, roots);
+    rec_reduce(d.rec, a);
+}
+
 }  // namespace
 
 static bool crops_sizes_ok(int32_t ny, int32_t nx, int32_t H, int32_t W, int32_t ch, int32_t cw) {
@@ -1012,6 +1257,58 @@ extern "C" int vpu_label_extract(uint16_t* labels, float* out, int32_t* rec, int
     const int nb = vpu_grid_for(((long long)H * W + 3) / 4, 256, 1024);
     label_extract_kernel<<<(unsigned)nb, 256, 0, ST>>>(labels, out, rec, H, W, (unsigned)label);
     return vpu_check_launch("vpu_label_extract");
+}
+
+extern "C" int vpu_regions_tidy_batched(const vpu_tidy_obj* objs, const vpu_tidy_obj* host_objs, int32_t n, float thr, void* stream) {
+    vpu_clear_stale_error();
+    char msg[256];
+    if (!objs || !host_objs || n < 1 || n > 65535 || !(thr >= 0.f && thr < 1.f)) {
+        vpu_set_error("regions_tidy_batched: null descriptors, n (1 <= n <= 65535) or thr (0 <= thr < 1)");
+        return VPU_ERR_ARG;
+    }
+    int64_t max_hw = 0;
+    bool seeds = false, largest = false;
+    for (int32_t k = 0; k < n; ++k) {
+        const vpu_tidy_obj& d = host_objs[k];
+        if (d.H < 1 || d.W < 1 || (int64_t)d.H * d.W > 0x7fffffffLL || !d.bits || !d.rec || !d.scratch ||
+            (!d.add && !d.total && (d.add_out || d.total_out)) || d.n_seeds < 0 || (d.n_seeds > 0 && !d.seeds) || d.min_area < 0 ||
+            d.max_hole < 0 || d.keep < VPU_TIDY_ALL || d.keep > VPU_TIDY_LARGEST) {
+            snprintf(msg, sizeof msg, "regions_tidy_batched: item %d: sizes (H, W >= 1, H * W < 2^31), a null bits, rec or scratch, an "
+                     "output map without an input, seeds, min_area or max_hole < 0, or keep (0: all, 1: seeded, 2: largest)", k);
+            vpu_set_error(msg);
+            return VPU_ERR_ARG;
+        }
+        const uintptr_t maps = reinterpret_cast<uintptr_t>(d.add) | reinterpret_cast<uintptr_t>(d.total) |
+                               reinterpret_cast<uintptr_t>(d.add_out) | reinterpret_cast<uintptr_t>(d.total_out) |
+                               reinterpret_cast<uintptr_t>(d.scratch);
+        if (maps % 16 || reinterpret_cast<uintptr_t>(d.bits) % 8 || reinterpret_cast<uintptr_t>(d.rec) % 4 ||
+            reinterpret_cast<uintptr_t>(d.seeds) % 4) {
+            snprintf(msg, sizeof msg, "regions_tidy_batched: item %d: a map or scratch not 16-byte, bits not 8-byte, rec or seeds not "
+                     "4-byte aligned", k);
+            vpu_set_error(msg);
+            return VPU_ERR_ALIGN;
+        }
+        const int64_t hw = (int64_t)d.H * d.W;
+        max_hw = hw > max_hw ? hw : max_hw;
+        seeds = seeds || d.n_seeds > 0;
+        largest = largest || d.keep == VPU_TIDY_LARGEST;
+    }
+    const dim3 pixels((unsigned)((max_hw + 255) / 256), (unsigned)n);
+    rec_init_kernel<3><<<(n + 63) / 64, 64, 0, ST>>>(objs, n);
+    tidy_init_kernel<<<pixels, 256, 0, ST>>>(objs, thr);
+    tidy_merge_kernel<true><<<pixels, 256, 0, ST>>>(objs);
+    tidy_flatten_kernel<0><<<pixels, 256, 0, ST>>>(objs);
+    if (seeds) tidy_seed_kernel<0><<<(unsigned)n, 256, 0, ST>>>(objs);
+    if (largest) tidy_largest_kernel<<<pixels, 256, 0, ST>>>(objs);
+    tidy_keep_kernel<<<pixels, 256, 0, ST>>>(objs);
+    tidy_merge_kernel<false><<<pixels, 256, 0, ST>>>(objs);
+    tidy_flatten_kernel<1><<<pixels, 256, 0, ST>>>(objs);
+    if (seeds) tidy_seed_kernel<1><<<(unsigned)n, 256, 0, ST>>>(objs);
+    tidy_fill_kernel<<<pixels, 256, 0, ST>>>(objs);
+    tidy_merge_kernel<true><<<pixels, 256, 0, ST>>>(objs);
+    const int nb = vpu_grid_for(max_hw, 1024, 128);
+    tidy_apply_kernel<<<dim3((unsigned)nb, (unsigned)n), 256, 0, ST>>>(objs, thr);
+    return vpu_check_launch("vpu_regions_tidy_batched");
 }
 
 // The launch geometry of (8) from the host's copy of the descriptors, after every check of them: bands_max and cols_max

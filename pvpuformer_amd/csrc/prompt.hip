@@ -2,6 +2,7 @@
 // bit-exact with the reference (isegm/model/is_vpu_model.py:189-291, isegm/model/ops.py:39-202, 347-379,
 // isegm/model/is_model.py:97-121).  Bandwidth-bound pointwise kernels (172.6 KB/img and 1.6 MB/img written).
 #include "vpu_common.h"
+#include "cc_union.h"
 #include "../../include/vpu_hip.h"
 
 #define ST reinterpret_cast<hipStream_t>(stream)
@@ -665,29 +666,7 @@ __global__ __launch_bounds__(256) void edt_rows_kernel(const uint8_t* __restrict
 // component of foreground pixel i (-1 on background).  Components ordered by their root are in the raster order of their
 // first pixel, i.e. the label order of scipy.ndimage.label / skimage.measure.label that max_connected_regions
 // (isegm/engine/trainer.py:1175-1190) scans.  The result does not depend on the order in which the unions happen.
-__device__ __forceinline__ int cc_find(int* __restrict__ lab, int i) {
-    // path halving: every visited node is re-pointed to its grandparent (parents only ever decrease towards the root,
-    // so a concurrent writer can at worst install another valid ancestor)
-    int r = i;
-    while (true) {
-        const int p = __hip_atomic_load(lab + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == r) return r;
-        const int gp = __hip_atomic_load(lab + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (gp != p) __hip_atomic_store(lab + r, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        r = p;
-    }
-}
-__device__ __forceinline__ void cc_union(int* __restrict__ lab, int a, int b) {
-    while (true) {
-        a = cc_find(lab, a);
-        b = cc_find(lab, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }          // a > b: hang the larger root under the smaller
-        const int old = atomicMin(lab + a, b);
-        if (old == a) return;                                  // a was still a root: linked
-        a = old;                                               // somebody re-parented a meanwhile: merge that parent with b
-    }
-}
+// cc_find / cc_union: cc_union.h (shared with the region clean-up of evalbatch.hip).
 // one block per image row: every foreground pixel starts as a child of the FIRST pixel of its horizontal run (inclusive
 // max-scan of "index after the last background pixel"), so the union step only has to join runs of adjacent rows
 __global__ __launch_bounds__(256) void cc_init_kernel(const uint8_t* __restrict__ mask, int* __restrict__ lab, int H, int W) {

@@ -17,6 +17,9 @@ public methods only (``open / close / predict / probs / get_states / set_states`
   R6  undo restores the object as it was before its last click or partial finish (a stack of at most ``max_undo``).
   R7  an initial mask stands in for ``parts`` until a partial finish or finish clears it.
   R8  reopen removes a committed label from ``labels`` and makes its pixels the initial mask.
+  R9  tidy drops small islands of R1's mask and fills its small holes (regions.py, rules T1-T8; the seeds are the object's
+      clicks): an undo snapshot first, then additive and parts / initial mask both take the edits 0.0 / 1.0, so R1's mask
+      is the cleaned one from then on.
 
 All of this is max, a strict compare and integer writes, done by ``vpu_annot_compose_batched`` / ``vpu_label_extract``
 (csrc/evalbatch.hip, section 7): what crosses to the host is the packed mask (``H * W / 8`` bytes) or the 32-byte record,
@@ -26,6 +29,7 @@ import numpy as np
 import torch
 
 from .clicker import Click, Clicker
+from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
 from .runs import KIND_LABELS, KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map, stack_objects
 from ._batchcore import PackedLayout, host_count_box, pack_mask, unpack_mask, upload_structs
 from .sessions import SessionPool
@@ -179,7 +183,8 @@ class AnnotationPool:
     ``readbacks`` counts the device-to-host synchronisations, the pool's included: a click on objects without parts and
     initial mask costs the pool's, otherwise one compose launch and one more read-back for those annotations together;
     ``finish`` one launch and one read-back (32 bytes), ``label_map`` one copy, ``reopen`` one read-back (32 bytes), ``undo``
-    one (the mask), ``partially_finish`` and ``current_prob`` none; ``label_runs`` two (the offsets, then 8 bytes per run) and
+    one (the mask), ``tidy`` one for all named annotations (``ops_regions``, replaceable by ``HostRegionOps()``),
+    ``partially_finish`` and ``current_prob`` none; ``label_runs`` two (the offsets, then 8 bytes per run) and
     ``export`` two, none when no object is finished.  ``ops`` holds the two device operations and may be replaced by
     ``HostAnnotOps()``; ``ops_runs`` holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``.
     ``load(aid, objects)`` and ``set_mask(aid, RunMap or COCO dict)`` bring run-length objects onto the device through
@@ -196,6 +201,7 @@ class AnnotationPool:
         self.device = self.pool.device
         self.ops = DeviceAnnotOps(self.device) if self.device.type == "cuda" else HostAnnotOps(self.device)
         self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
+        self.ops_regions = DeviceRegionOps(self.device) if self.device.type == "cuda" else HostRegionOps(self.device)
         self._held = {}
         self._own_readbacks = 0
 
@@ -291,6 +297,40 @@ class AnnotationPool:
         if a.empty:
             return np.zeros((a.H, a.W), dtype=bool)
         return self._masks([a])[aid]
+
+    def tidy(self, aids, min_area=0, max_hole=0, keep="all"):
+        """R9: the region clean-up of regions.py (rules T1-T8) on R1's mask of the named annotations' objects -> {aid: mask}.
+        Components below ``min_area`` pixels are dropped, holes of at most ``max_hole`` pixels filled (None: every hole);
+        ``keep``: "all", "seeded" or "largest".  The seeds are the object's clicks.  An undo snapshot is pushed first; then both
+        maps take the edits (0.0 on dropped pixels, 1.0 on filled ones): the session's previous prediction when the object has
+        clicks, and a NEW tensor in place of the parts or the initial mask when there is one (a snapshot may hold the old one,
+        which is never written).  The click list, ``click_indx_offset`` and the ZoomIn state stay.  One launch group and one
+        read-back for all of them; an empty object gives an all-False mask and pushes nothing."""
+        min_area, max_hole = check_tidy_args("AnnotationPool.tidy", min_area, max_hole, keep)
+        if not 0.0 <= self.prob_thresh < 1.0:   # the edits 0.0 and 1.0 must fall on the clear and the set side of it
+            raise ValueError(f"AnnotationPool.tidy: prob_thresh {self.prob_thresh} is outside [0, 1)")
+        anns = [self._ann(aid) for aid in aids]
+        out = {a.aid: np.zeros((a.H, a.W), dtype=bool) for a in anns if a.empty}
+        live, items = [a for a in anns if not a.empty], []
+        for a in live:
+            self._snapshot(a)
+            add, total = self._additive(a), a.total
+            items.append(TidyItem(a.H, a.W, add=add, total=total, add_out=None if add is None else torch.empty_like(add),
+                                  total_out=None if total is None else torch.empty_like(total),
+                                  seeds=click_seeds(a.clicker.get_clicks()), min_area=min_area, max_hole=max_hole, keep=keep))
+        if not live:
+            return out
+        got = self.ops_regions.tidy(items, self.prob_thresh, "masks")
+        self._own_readbacks += 1
+        for a, it, (_, mask) in zip(live, items, got):
+            if it.add_out is not None:
+                self.pool.set_states(a.aid, dict(self.pool.get_states(a.aid), prev_prediction=it.add_out))
+            if a.mask is not None:
+                a.mask = it.total_out
+            elif a.parts is not None:
+                a.parts = it.total_out
+            out[a.aid] = mask
+        return {a.aid: out[a.aid] for a in anns}
 
     def partially_finish(self, aid):
         """R4.  No synchronisation: one launch that writes the new parts."""

@@ -37,6 +37,7 @@ from ..model.scribble import scribble_profiles
 from ._batchcore import (PackedLayout, ZoomHost, host_count_box, host_roi_paste, host_roi_resize, n_words, pack_mask,  # noqa: F401
                          unpack_mask, upload_structs)
 from .batched import _load_image, _padded_slot, batchable
+from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
 from .runs import KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map
 
 
@@ -227,8 +228,11 @@ class SessionPool(ZoomHost):
     ``pool.close(sid)``; ``pool.mask_runs(sids=None) -> {sid: RunMap}``, the masks as run-length maps (runs.py).
     ``max_batch``: sessions per forward (default ``max_sessions``); a size group with more runs in chunks.
     ``max_stroke_points``: the longest stroke ``predict`` takes.
-    ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``).  ``ops_runs``
-    holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``."""
+    ``pool.tidy(sids=None, min_area=0, max_hole=0, keep="all", seeds=None) -> {sid: mask}``: small islands dropped and small
+    holes filled on the device (regions.py).
+    ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``, one per
+    ``tidy``).  ``ops_runs`` holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``; ``ops_regions``
+    holds the region clean-up and may be replaced by ``HostRegionOps()``."""
 
     def __init__(self, predictor, max_sessions=8, pred_thr=0.49, max_batch=None, max_stroke_points=1024):
         if not batchable(predictor):
@@ -244,6 +248,7 @@ class SessionPool(ZoomHost):
         self.prompt_img = int(size[0]) if size is not None else None
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
         self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
+        self.ops_regions = DeviceRegionOps(self.device) if self.device.type == "cuda" else HostRegionOps(self.device)
         self._slots = [None] * self.max_sessions
         self.readbacks = self.forwards = 0
 
@@ -284,6 +289,35 @@ class SessionPool(ZoomHost):
         maps = self.ops_runs.encode([(s.canvas[s.prev], KIND_PROB, self.pred_thr) for s in held])
         self.readbacks += 2
         return {s.sid: rm for s, rm in zip(held, maps)}
+
+    def tidy(self, sids=None, min_area=0, max_hole=0, keep="all", seeds=None):
+        """Region clean-up (regions.py, rules T1-T8) of the mask ``probs(sid) > pred_thr`` of the named sessions (default: all
+        open ones) -> {sid: bool ndarray [H, W]}: components below ``min_area`` pixels dropped, holes of at most ``max_hole``
+        pixels filled (None: every hole); ``keep``: "all", "seeded" (only components that hold a positive seed: empty
+        without one) or "largest".  The seeds are the clicks of the session's last ``predict`` -- a component with a positive
+        click is always kept, a hole with a negative click never filled -- or ``seeds[sid]``, a list of ``Click`` or of
+        (is_positive, (row, col)).  The session's previous prediction becomes the edited map (0.0 on dropped pixels, 1.0 on
+        filled ones), so the next click's network input sees the cleaned mask; the ZoomIn state and the generator are not
+        touched.  One call for all of them, one read-back.  A session without a prediction yet gives an all-False mask."""
+        min_area, max_hole = check_tidy_args("SessionPool.tidy", min_area, max_hole, keep)
+        if not 0.0 <= self.pred_thr < 1.0:      # the edits 0.0 and 1.0 must fall on the clear and the set side of it
+            raise ValueError(f"SessionPool.tidy: pred_thr {self.pred_thr} is outside [0, 1)")
+        if sids is None:
+            sids = [sid for sid, held in enumerate(self._slots) if held is not None]
+        held = [self._session(sid) for sid in sids]
+        for sid in (seeds or {}):
+            if sid not in sids:
+                raise ValueError(f"SessionPool.tidy: seeds names session {sid!r}, which is not among the sessions of this call")
+        if not held:
+            return {}
+        items = []
+        for s in held:
+            prev = s.canvas[s.prev]
+            items.append(TidyItem(s.H, s.W, add=prev, add_out=prev, min_area=min_area, max_hole=max_hole, keep=keep,
+                                  seeds=click_seeds(seeds[s.sid] if seeds and s.sid in seeds else s.clicks)))
+        got = self.ops_regions.tidy(items, self.pred_thr, "masks")
+        self.readbacks += 1
+        return {s.sid: mask for s, (_, mask) in zip(held, got)}
 
     def get_states(self, sid):
         s = self._session(sid)

@@ -530,6 +530,24 @@ def runs_decode_batched(objs, host_objs, n):
     _lib.call("vpu_runs_decode_batched", ptr(objs), ptr(host_objs), n, _stream())
 
 
+TIDY_ALL, TIDY_SEEDED, TIDY_LARGEST = 0, 1, 2       # VPU_TIDY_* (include/vpu_hip.h)
+
+
+def tidy_scratch_ints(hw):
+    """VPU_TIDY_SCRATCH_INTS: the int32 entries of one item's scratch slice, 12 bytes per pixel and a 16-byte header."""
+    return 3 * int(hw) + 4
+
+
+def regions_tidy_batched(objs, host_objs, n, thr):
+    """n maps (objs: device array of vpu_tidy_obj, host_objs: the host tensor it was copied from) cleaned by rules T1-T8: small
+    islands dropped, small holes filled, the fp32 maps copied with the two edits, packed mask and record written
+    (vpu_regions_tidy_batched)."""
+    nbytes = n * C.sizeof(_lib.TidyObj)
+    assert n >= 1 and objs.is_cuda and objs.is_contiguous() and objs.numel() * objs.element_size() >= nbytes
+    assert not host_objs.is_cuda and host_objs.is_contiguous() and host_objs.numel() * host_objs.element_size() >= nbytes
+    _lib.call("vpu_regions_tidy_batched", ptr(objs), ptr(host_objs), n, float(thr), _stream())
+
+
 def click_keys_batched(objs, n, Hm, Wm, max_hw, device):
     """The Clicker's (false-negative, false-positive) keys of n objects into their ``out`` slots (vpu_click_keys_batched)."""
     err = torch.empty(2 * n, Hm, Wm, device=device, dtype=torch.uint8)
