@@ -498,6 +498,44 @@ typedef struct vpu_tidy_obj {
  * n_seeds > 0, min_area or max_hole < 0, an unknown keep, thr outside [0, 1) (the edits 0.0 and 1.0 must fall on the clear and the
  * set side of it); VPU_ERR_ALIGN: a misaligned map, bits, rec, seeds or scratch pointer.  Neither allocates nor synchronises. */
 int vpu_regions_tidy_batched(const vpu_tidy_obj* objs, const vpu_tidy_obj* host_objs, int32_t n, float thr, void* stream);
+/* Outlines (pvpuformer_amd/isegm/inference/outlines.py): the closed polygon loops of the binary map M of n
+ * items of different sizes, rules O1-O6: pixel (r, c) is the unit square [c, c + 1] x [r, r + 1] in (x, y), y down; a boundary
+ * edge has the set pixel on its right; at a saddle the walk turns left (foreground 8-connected, holes 4-connected); a loop is
+ * its corners in the order of travel from the corner of smallest (y, x); loops are ordered by that corner.
+ *   kind 0: src fp32 [H][W], 16-byte aligned, M = src > thr (strict, in fp32; NaN is outside the contract); label is not read;
+ *   kind 1: src uint16 [H][W], 8-byte aligned, M = src == label; thr is not read. */
+typedef struct vpu_outline_obj {
+    const void* src;
+    int32_t H, W, kind;
+    float thr;
+    int32_t label, pad;
+} vpu_outline_obj;
+/* The lattice of an item is (H + 1) x (W + 1) vertices.  A wave covers VPU_OUTLINE_COLS consecutive x of a lattice row and walks
+ * VPU_OUTLINE_BAND_ROWS lattice rows; groups = ceil((W + 1) / VPU_OUTLINE_COLS), bands = ceil((H + 1) / VPU_OUTLINE_BAND_ROWS).
+ * objs is the DEVICE array of the n descriptors, host_objs the staging copy in host memory: the wrappers read it and refuse
+ * before any launch -- VPU_ERR_ARG: n outside 1 .. 65535, a NULL src, H or W < 1, 2 (H + 1) (W + 1) summed over the items at or
+ * above 2^31, a kind other than 0 / 1, kind 1 with a label outside 0 .. 65535, kind 0 with thr outside [0, 1), a NULL or short
+ * buffer, a negative cap; VPU_ERR_ALIGN: a misaligned src (16 bytes fp32, 8 bytes labels), work (16), points or offsets (8).
+ * vpu_outline_count_batched (two launches): scratch int32 [scratch_len], scratch_len >= n * (rs + cs) with rs = the largest
+ * (H + 1) * groups and cs = the largest (W + 1) * bands of the items.  Afterwards scratch[k * rs + y * groups_k + g] is the
+ * row-major rank of the first corner of item k in lattice row y, column group g, and scratch[n * rs + k * cs + x * bands_k + b]
+ * the column-major rank of the first corner in lattice column x, band b, both over all items in order; header int32 [n + 1]:
+ * header[k] = the rank of item k's first corner, header[n] = V, the number of corners of all items.
+ * vpu_outline_trace_batched (4 + ceil(log2(max V_k)) launches, none when V == 0): scratch and header as the count call left
+ * them, host_header the header read back to the host; work int32 [work_len], work_len >= VPU_OUTLINE_WORK_INTS(V).  points
+ * int32 [cap][2] = (x, y) of every corner: item after item, loop after loop, in the order of travel; only entries below cap are
+ * written, one 8-byte store each.  offsets int32 [loop_cap]: offsets[l] = the entry in points at which loop l (counted over all
+ * items) begins, offsets[L] = V after the last of the L loops; only entries below loop_cap are written (L <= V / 4).
+ * item_loops int32 [n + 1]: the index of each item's first loop, item_loops[n] = L.  Neither allocates nor synchronises. */
+#define VPU_OUTLINE_BAND_ROWS 32
+#define VPU_OUTLINE_COLS 64
+#define VPU_OUTLINE_WORK_INTS(v) (16 * (int64_t)(v) + 2)
+int vpu_outline_count_batched(const vpu_outline_obj* objs, const vpu_outline_obj* host_objs, int32_t n, int32_t* scratch,
+                              int64_t scratch_len, int32_t* header, void* stream);
+int vpu_outline_trace_batched(const vpu_outline_obj* objs, const vpu_outline_obj* host_objs, int32_t n, const int32_t* scratch,
+                              int64_t scratch_len, const int32_t* header, const int32_t* host_header, int32_t* work,
+                              int64_t work_len, int32_t* points, int32_t cap, int32_t* offsets, int32_t loop_cap,
+                              int32_t* item_loops, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

@@ -90,6 +90,12 @@ class UnrunObj(C.Structure):
                 ("kind", C.c_int32), ("label", C.c_int32), ("pad", C.c_int32)]
 
 
+class OutlineObj(C.Structure):
+    """vpu_outline_obj (include/vpu_hip.h): one map of vpu_outline_count_batched / vpu_outline_trace_batched."""
+    _fields_ = [("src", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32), ("thr", C.c_float),
+                ("label", C.c_int32), ("pad", C.c_int32)]
+
+
 class TidyObj(C.Structure):
     """vpu_tidy_obj (include/vpu_hip.h): one map of vpu_regions_tidy_batched."""
     _fields_ = [("add", C.c_void_p), ("total", C.c_void_p), ("add_out", C.c_void_p), ("total_out", C.c_void_p),
@@ -153,6 +159,8 @@ SIGNATURES = {
     "vpu_runs_write_batched": [_P, _P, _I, _P, _L, _P, _I, _P],
     "vpu_runs_decode_batched": [_P, _P, _I, _P],
     "vpu_regions_tidy_batched": [_P, _P, _I, _F, _P],
+    "vpu_outline_count_batched": [_P, _P, _I, _P, _L, _P, _P],
+    "vpu_outline_trace_batched": [_P, _P, _I, _P, _L, _P, _P, _P, _L, _P, _I, _P, _I, _P, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

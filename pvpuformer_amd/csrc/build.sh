@@ -13,7 +13,7 @@ if [ "$1" = "diag" ]; then FLAGS="$FLAGS -DVPU_DIAG -DVPU_LAB"; OUT=libvpu_hip_d
 if [ "$1" = "x" ]; then FLAGS="$FLAGS $VPU_X_FLAGS"; OUT=libvpu_hip_x.so; BUILD=build_x; fi
 mkdir -p $BUILD
 pids=()
-for f in gemm gemm_k5 attention rowops spatial prompt loss optim evalbatch; do
+for f in gemm gemm_k5 attention rowops spatial prompt loss optim evalbatch outline; do
   # attention.hip: MFMA results straight into VGPRs (the softmax consumes every score tile with VALU instructions; with the
   # accumulator-register form hipcc copies each tile through v_accvgpr_read and the kernels drop to one wave per SIMD)
   EXTRA=""; [ $f = attention ] && EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1"

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .clicker import Click, Clicker
+from .outlines import DeviceOutlineOps, HostOutlineOps
 from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
 from .runs import KIND_LABELS, KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map, stack_objects
 from ._batchcore import PackedLayout, host_count_box, pack_mask, unpack_mask, upload_structs
@@ -178,14 +179,15 @@ class AnnotationPool:
     """``ann = AnnotationPool(predictor, max_images=8, prob_thresh=0.5, max_undo=32, **session_pool_kwargs)``; ``predictor``:
     any predictor ``SessionPool`` accepts.  ``aid = ann.open(image, seed=None)``; ``ann.click({aid: click, ...}, boxes=None,
     strokes=None) -> {aid: bool ndarray [H, W]}``; ``undo / partially_finish / finish / set_mask / load / reopen / label_map /
-    label_runs / export / objects / object_count / current_prob / close`` take an ``aid``.
+    label_runs / label_outlines / export / objects / object_count / current_prob / close`` take an ``aid``.
 
     ``readbacks`` counts the device-to-host synchronisations, the pool's included: a click on objects without parts and
     initial mask costs the pool's, otherwise one compose launch and one more read-back for those annotations together;
     ``finish`` one launch and one read-back (32 bytes), ``label_map`` one copy, ``reopen`` one read-back (32 bytes), ``undo``
     one (the mask), ``tidy`` one for all named annotations (``ops_regions``, replaceable by ``HostRegionOps()``),
     ``partially_finish`` and ``current_prob`` none; ``label_runs`` two (the offsets, then 8 bytes per run) and
-    ``export`` two, none when no object is finished.  ``ops`` holds the two device operations and may be replaced by
+    ``export`` two, none when no object is finished; ``label_outlines`` two (``ops_outlines``, replaceable by
+    ``HostOutlineOps()``) and ``export(aid, polygons=True)`` two more.  ``ops`` holds the two device operations and may be replaced by
     ``HostAnnotOps()``; ``ops_runs`` holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``.
     ``load(aid, objects)`` and ``set_mask(aid, RunMap or COCO dict)`` bring run-length objects onto the device through
     ``ops_runs.decode``: one copy up, one launch, no read-back."""
@@ -202,6 +204,7 @@ class AnnotationPool:
         self.ops = DeviceAnnotOps(self.device) if self.device.type == "cuda" else HostAnnotOps(self.device)
         self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
         self.ops_regions = DeviceRegionOps(self.device) if self.device.type == "cuda" else HostRegionOps(self.device)
+        self.ops_outlines = DeviceOutlineOps(self.device) if self.device.type == "cuda" else HostOutlineOps(self.device)
         self._held = {}
         self._own_readbacks = 0
 
@@ -436,17 +439,50 @@ class AnnotationPool:
         self._own_readbacks += 2
         return rm
 
-    def export(self, aid):
+    def label_outlines(self, aid, labels=None, preview=True):
+        """{label: Outline} (outlines.py): the polygon loops of ``label_map(aid, preview) == label`` for every label of
+        ``labels`` (integers in 0 .. 65535; default: every committed object's label and, with ``preview``, that of the object
+        in progress), traced on the device from the map built as ``label_map`` builds it.  One item per label, all in ONE trace:
+        two read-backs.  A label no pixel holds gives an outline without loops; without a label to trace the result is {} and
+        the device is not touched."""
+        a = self._ann(aid)
+        drawn = preview and not a.empty
+        if labels is None:
+            labels = [r["label"] for r in a.records] + ([self._next_label(a)] if drawn else [])
+        labels = list(labels)
+        for label in labels:
+            if not (isinstance(label, (int, np.integer)) and 0 <= label <= MAX_LABEL):
+                raise ValueError(f"AnnotationPool: label {label!r} is not an integer in 0 .. {MAX_LABEL}")
+        if not labels:
+            return {}
+        source = a.labels
+        if drawn:
+            source = a.labels.clone()
+            self.ops.compose([self._item(a, labels=source, label=self._next_label(a), mode=2)], self.prob_thresh, None)
+        got = self.ops_outlines.trace([(source, KIND_LABELS, 0.0, int(label)) for label in labels])
+        self._own_readbacks += 2
+        return {int(label): outline for label, outline in zip(labels, got)}
+
+    def export(self, aid, polygons=False):
         """The finished objects in COCO's form: the records of ``objects(aid)``, each with ``segmentation = dict(size=[H, W],
         counts=[...])``, the uncompressed run-length encoding of the pixels that hold its label now (an object that later
         ones have covered keeps its record; its counts are then ``[H * W]``).  ONE encode of the committed label map, without
-        the object in progress: two read-backs.  [] without touching the device when no object is finished."""
+        the object in progress: two read-backs.  With ``polygons`` each record also carries ``polygons``, the outer loops of
+        those pixels in COCO's polygon form (``Outline.to_coco()``), and ``polygon_holes``, the number of hole loops that form
+        leaves out, from ONE trace of the committed label map: two more read-backs.  [] without touching the device when no
+        object is finished."""
         a = self._ann(aid)
         if not a.records:
             return []
         rm, = self.ops_runs.encode([(a.labels, KIND_LABELS, 0.0)])
         self._own_readbacks += 2
-        return [dict(r, segmentation=rm.to_coco(r["label"])) for r in a.records]
+        out = [dict(r, segmentation=rm.to_coco(r["label"])) for r in a.records]
+        if polygons:
+            outlines = self.label_outlines(aid, [r["label"] for r in a.records], preview=False)
+            for e in out:
+                e["polygons"] = outlines[e["label"]].to_coco()
+                e["polygon_holes"] = int(outlines[e["label"]].holes().sum())
+        return out
 
     def load(self, aid, objects, keep_labels=False):
         """Finished objects into a fresh annotation -> their records.  ``objects``: a list of ``RunMap``s (a pixel set where

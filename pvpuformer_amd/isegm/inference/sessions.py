@@ -38,6 +38,7 @@ from ._batchcore import (PackedLayout, ZoomHost, host_count_box, host_roi_paste,
                          unpack_mask, upload_structs)
 from .batched import _load_image, _padded_slot, batchable
 from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
+from .outlines import DeviceOutlineOps, HostOutlineOps
 from .runs import KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map
 
 
@@ -225,14 +226,16 @@ class SessionPool(ZoomHost):
 
     ``sid = pool.open(image, seed=None)``; ``pool.predict({sid: clicks, ...}, prev_masks=None, boxes=None, strokes=None) ->
     {sid: bool ndarray [H, W]}``; ``pool.probs(sid)``; ``pool.get_states(sid)`` / ``pool.set_states(sid, st)``;
-    ``pool.close(sid)``; ``pool.mask_runs(sids=None) -> {sid: RunMap}``, the masks as run-length maps (runs.py).
+    ``pool.close(sid)``; ``pool.mask_runs(sids=None) -> {sid: RunMap}``, the masks as run-length maps (runs.py);
+    ``pool.mask_outlines(sids=None) -> {sid: Outline}``, the masks as polygon loops (outlines.py).
     ``max_batch``: sessions per forward (default ``max_sessions``); a size group with more runs in chunks.
     ``max_stroke_points``: the longest stroke ``predict`` takes.
     ``pool.tidy(sids=None, min_area=0, max_hole=0, keep="all", seeds=None) -> {sid: mask}``: small islands dropped and small
     holes filled on the device (regions.py).
     ``readbacks`` counts the device-to-host synchronisations (one per forward round, two per ``mask_runs``, one per
-    ``tidy``).  ``ops_runs`` holds the run-length encoder and decoder and may be replaced by ``HostRunOps()``; ``ops_regions``
-    holds the region clean-up and may be replaced by ``HostRegionOps()``."""
+    ``tidy``, two per ``mask_outlines``).  ``ops_runs`` holds the run-length encoder and decoder and may be replaced by
+    ``HostRunOps()``; ``ops_regions`` holds the region clean-up and may be replaced by ``HostRegionOps()``; ``ops_outlines`` holds
+    the outline tracer and may be replaced by ``HostOutlineOps()``."""
 
     def __init__(self, predictor, max_sessions=8, pred_thr=0.49, max_batch=None, max_stroke_points=1024):
         if not batchable(predictor):
@@ -249,6 +252,7 @@ class SessionPool(ZoomHost):
         self.ops = _DeviceOps(self.device) if self.device.type == "cuda" else _HostOps(self.device)
         self.ops_runs = DeviceRunOps(self.device) if self.device.type == "cuda" else HostRunOps(self.device)
         self.ops_regions = DeviceRegionOps(self.device) if self.device.type == "cuda" else HostRegionOps(self.device)
+        self.ops_outlines = DeviceOutlineOps(self.device) if self.device.type == "cuda" else HostOutlineOps(self.device)
         self._slots = [None] * self.max_sessions
         self.readbacks = self.forwards = 0
 
@@ -289,6 +293,20 @@ class SessionPool(ZoomHost):
         maps = self.ops_runs.encode([(s.canvas[s.prev], KIND_PROB, self.pred_thr) for s in held])
         self.readbacks += 2
         return {s.sid: rm for s, rm in zip(held, maps)}
+
+    def mask_outlines(self, sids=None):
+        """{sid: Outline} (outlines.py) of the mask ``probs(sid) > pred_thr`` of the named sessions (default: all open ones):
+        its polygon loops on the pixel lattice, so ``outline.to_coco()`` is the mask in COCO's polygon form.  One trace for all
+        of them: two read-backs (the offsets, then 8 bytes per corner).  A session without a prediction yet gives an outline
+        without loops; no session's state is touched."""
+        if sids is None:
+            sids = [sid for sid, held in enumerate(self._slots) if held is not None]
+        held = [self._session(sid) for sid in sids]
+        if not held:
+            return {}
+        got = self.ops_outlines.trace([(s.canvas[s.prev], KIND_PROB, self.pred_thr, 0) for s in held])
+        self.readbacks += 2
+        return {s.sid: outline for s, outline in zip(held, got)}
 
     def tidy(self, sids=None, min_area=0, max_hole=0, keep="all", seeds=None):
         """Region clean-up (regions.py, rules T1-T8) of the mask ``probs(sid) > pred_thr`` of the named sessions (default: all

@@ -530,6 +530,60 @@ def runs_decode_batched(objs, host_objs, n):
     _lib.call("vpu_runs_decode_batched", ptr(objs), ptr(host_objs), n, _stream())
 
 
+OUTLINE_BAND_ROWS = 32      # VPU_OUTLINE_BAND_ROWS (include/vpu_hip.h): lattice rows that one wave walks
+OUTLINE_COLS = 64           # VPU_OUTLINE_COLS: lattice columns per wave
+
+
+def outline_scratch_len(sizes):
+    """Entries of the int32 scratch array of an outline call over maps of ``sizes`` [(H, W)]: n * (the largest (H + 1) * groups
+    + the largest (W + 1) * bands) over the (H + 1) x (W + 1) lattices."""
+    rows = max((H + 1) * ((W + OUTLINE_COLS) // OUTLINE_COLS) for H, W in sizes)
+    cols = max((W + 1) * ((H + OUTLINE_BAND_ROWS) // OUTLINE_BAND_ROWS) for H, W in sizes)
+    return len(sizes) * (rows + cols)
+
+
+def outline_work_len(corners):
+    """VPU_OUTLINE_WORK_INTS: entries of the int32 work array of ``outline_trace_batched`` for ``corners`` corners in all."""
+    return 16 * int(corners) + 2
+
+
+def _outline_check(objs, host_objs, n, scratch):
+    nbytes = n * C.sizeof(_lib.OutlineObj)
+    assert n >= 1 and objs.is_cuda and objs.is_contiguous() and objs.numel() * objs.element_size() >= nbytes
+    assert not host_objs.is_cuda and host_objs.is_contiguous() and host_objs.numel() * host_objs.element_size() >= nbytes
+    assert scratch.is_cuda and scratch.dtype == torch.int32 and scratch.is_contiguous()
+
+
+def outline_count_batched(objs, host_objs, n, scratch, header):
+    """Corners of n maps (objs: device array of vpu_outline_obj, host_objs: the host tensor it was copied from) counted per
+    (lattice row, column group) and per (lattice column, band) into ``scratch`` and scanned in place; header int32 [n + 1] =
+    each item's first rank and the total (vpu_outline_count_batched)."""
+    _outline_check(objs, host_objs, n, scratch)
+    assert header.is_cuda and header.dtype == torch.int32 and header.is_contiguous() and header.numel() >= n + 1
+    _lib.call("vpu_outline_count_batched", ptr(objs), ptr(host_objs), n, ptr(scratch), scratch.numel(), ptr(header), _stream())
+
+
+def outline_trace_batched(objs, host_objs, n, scratch, header, host_header, work, points, offsets, item_loops, cap=None,
+                          loop_cap=None):
+    """The loops of the n maps after ``outline_count_batched`` left ``scratch`` and ``header`` (``host_header``: int32 host
+    tensor, the header read back): points int32 [*, 2] = (x, y) of every corner in loop order, offsets int32 [*] = where each
+    loop begins and, behind the last, the total, item_loops int32 [n + 1] = each item's first loop and the number of loops.
+    Entries at or beyond ``cap`` / ``loop_cap`` (default: all of ``points`` / ``offsets``) are not written
+    (vpu_outline_trace_batched)."""
+    _outline_check(objs, host_objs, n, scratch)
+    assert header.is_cuda and header.dtype == torch.int32 and header.is_contiguous() and header.numel() >= n + 1
+    assert not host_header.is_cuda and host_header.dtype == torch.int32 and host_header.is_contiguous() and host_header.numel() >= n + 1
+    assert work.is_cuda and work.dtype == torch.int32 and work.is_contiguous()
+    assert points.is_cuda and points.dtype == torch.int32 and points.is_contiguous() and points.dim() == 2 and points.shape[1] == 2
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.dim() == 1
+    assert item_loops.is_cuda and item_loops.dtype == torch.int32 and item_loops.is_contiguous() and item_loops.numel() >= n + 1
+    cap = points.shape[0] if cap is None else int(cap)
+    loop_cap = offsets.shape[0] if loop_cap is None else int(loop_cap)
+    assert cap <= points.shape[0] and loop_cap <= offsets.shape[0]
+    _lib.call("vpu_outline_trace_batched", ptr(objs), ptr(host_objs), n, ptr(scratch), scratch.numel(), ptr(header), ptr(host_header),
+              ptr(work), work.numel(), ptr(points), cap, ptr(offsets), loop_cap, ptr(item_loops), _stream())
+
+
 TIDY_ALL, TIDY_SEEDED, TIDY_LARGEST = 0, 1, 2       # VPU_TIDY_* (include/vpu_hip.h)
 
 
