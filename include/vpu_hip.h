@@ -536,6 +536,31 @@ int vpu_outline_trace_batched(const vpu_outline_obj* objs, const vpu_outline_obj
                               int64_t scratch_len, const int32_t* header, const int32_t* host_header, int32_t* work,
                               int64_t work_len, int32_t* points, int32_t cap, int32_t* offsets, int32_t loop_cap,
                               int32_t* item_loops, void* stream);
+/* Simplified polygons (pvpuformer_amd/isegm/inference/polygons.py): Douglas-Peucker, rules S1-S6, over the
+ * closed loops that vpu_outline_trace_batched left on the device; every decision is a comparison of int64 products below 2^58, so
+ * the result equals a sequential reference element for element.  points int32 [V][2], offsets int32 [>= L + 1] and item_loops
+ * int32 [n + 1] are the trace's outputs (device memory, read only); L = item_loops[n] is read on the device and clamped to
+ * loop_max, the caller's bound (V / 4 after a trace), and every offset is clamped into [0, V].  Coordinates must lie in
+ * 0 .. 8191.  t = the tolerance in quarter pixels, 0 .. 4096.  short_form: which split kernel takes the loops of at most
+ * VPU_SIMPLIFY_SHORT corners, 0 = form A (one workgroup of VPU_SIMPLIFY_THREADS per loop, any length), 1 = form B (one wave per
+ * loop); both write the same bytes.  work int32 [work_len], 16-byte aligned, work_len >= VPU_SIMPLIFY_WORK_INTS(V, loop_max).
+ * Three or four launches, none when V == 0 or loop_max == 0:
+ *   out_points int32 [cap][2]: the kept corners of the surviving loops, loop after loop; only entries below cap are written;
+ *   out_offsets int32 [loop_cap]: where each surviving loop begins, and V' behind the last; out_hole uint8 [loop_cap]: 1 for a
+ *   loop whose EXACT signed area is negative; only entries below loop_cap are written;
+ *   firsts int32 [2 (n + 1) + 4]: firsts[k] = the first surviving loop of item k (firsts[n] = L'), firsts[n + 1 + k] = its first
+ *   point (firsts[2 n + 1] = V'), then {V', L', dropped loops, the most rounds one loop took}: always the true totals.
+ * Refused before any launch -- VPU_ERR_ARG: a NULL points, offsets, item_loops, firsts or (with a positive cap) output, n < 1,
+ * V, loop_max, cap or loop_cap < 0, t outside 0 .. 4096, short_form outside 0 / 1, a NULL or short work; VPU_ERR_ALIGN: work not
+ * 16-byte, points, out_points, offsets or out_offsets not 8-byte, item_loops or firsts not 4-byte aligned.  Neither allocates
+ * nor synchronises. */
+#define VPU_SIMPLIFY_THREADS 256
+#define VPU_SIMPLIFY_SHORT 64
+#define VPU_SIMPLIFY_WORK_INTS(v, l) (10 * (int64_t)(v) + 5 * (int64_t)(l) + 8)
+int vpu_outline_simplify_batched(const int32_t* points, const int32_t* offsets, const int32_t* item_loops, int32_t n, int32_t V,
+                                 int32_t loop_max, int32_t t, int32_t short_form, int32_t* work, int64_t work_len,
+                                 int32_t* out_points, int32_t cap, int32_t* out_offsets, int32_t loop_cap, uint8_t* out_hole,
+                                 int32_t* firsts, void* stream);
 /* Box prompts of a batch of objects without a host round trip (BasePredictor.get_vqu_prediction, base.py:114-121, then
  * cal_box(as_allmask=False, jitter_box=False), trainer.py:1061-1131).  One row per object, or per object's flip copy:
  *   prev fp32 [H][W] (previous prediction), gt (== 1) / valid (!= ignore) uint8 [H][W] (the sequential path resizes the

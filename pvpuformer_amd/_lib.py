@@ -161,6 +161,7 @@ SIGNATURES = {
     "vpu_regions_tidy_batched": [_P, _P, _I, _F, _P],
     "vpu_outline_count_batched": [_P, _P, _I, _P, _L, _P, _P],
     "vpu_outline_trace_batched": [_P, _P, _I, _P, _L, _P, _P, _P, _L, _P, _I, _P, _I, _P, _P],
+    "vpu_outline_simplify_batched": [_P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _I, _P, _I, _P, _P, _P],
     "vpu_click_keys_batched": [_P, _I, _P, _P, _P, _I, _I, _I, _P],
     "vpu_box_prompts_batched": [_P, _I, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "vpu_crops_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -413,3 +413,401 @@ extern "C" int vpu_outline_trace_batched(const vpu_outline_obj* objs, const vpu_
                                                                             offsets, loop_cap, item_loops);
     return vpu_check_launch("vpu_outline_trace_batched");
 }
+
+// ===================================================================================================================
+// Simplified polygons (pvpuformer_amd/isegm/inference/polygons.py): Douglas-Peucker, rules S1-S6 of
+// include/vpu_hip.h, over the loops the trace left on the device.  Workgroups do not communicate: no grid barrier, and no
+// workgroup reads what another one of the same launch writes.
+//
+// Rounds instead of recursion.  Every position that is not kept and whose chain may still split knows its chain (i, j), the kept
+// positions around it.  A round finds each chain's k of largest num (the smallest k on ties) and applies S4; a chain that does
+// not split never will, so its positions retire.  After a split every position of the chain compares itself with k and takes
+// (i, k) or (k, j): no scan is needed to find the new chain ends.  S3 is the first round: S4 on the chain (0, n), whose ends are
+// both P_0, with t = 0.  The kept set does not depend on the order of the splits, so it is the sequential one.
+namespace {
+
+// work int32 [10 V + 5 Lm + 8] (16-byte aligned), Lm = loop_max: the largest num of the chain that begins at a position, in two
+// copies that the rounds use in turn (int64), the smallest position that has it (two copies), per position its chain (i, j) or
+// {-1, next kept} once kept or {-2, -} once retired, its rank among the kept of its loop (-1: not kept) and its loop; per loop
+// the kept count (0: dropped), the hole flag, the rounds, and the exclusive sums of surviving loops and kept points.
+struct SimplifyWork {
+    long long* best;
+    int *bpos, *rank, *loopof, *cnt, *lhole, *rounds, *nidx, *noff;
+    int2* state;
+};
+
+__host__ __device__ inline SimplifyWork simplify_work(int32_t* work, int64_t V, int64_t Lm) {
+    SimplifyWork w;
+    w.best = reinterpret_cast<long long*>(work);                      // [2][V]
+    w.state = reinterpret_cast<int2*>(work + 4 * V);                  // [V]
+    w.bpos = work + 6 * V;                                            // [2][V]
+    w.rank = work + 8 * V;
+    w.loopof = work + 9 * V;
+    w.cnt = work + 10 * V;
+    w.lhole = w.cnt + Lm;
+    w.rounds = w.lhole + Lm;
+    w.nidx = w.rounds + Lm;                                           // [Lm + 1]
+    w.noff = w.nidx + Lm + 1;                                         // [Lm + 1]
+    return w;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the loop l of the trace's output with every index clamped: its first corner and its length
+__device__ __forceinline__ void simplify_loop(const int* __restrict__ offsets, int l, int V, int& a, int& n) {
+    a = clampi(offsets[l], 0, V);
+    n = clampi(offsets[l + 1], a, V) - a;
+}
+
+// S2: the squared distance of P to the segment A B as num / den.  Coordinates lie in 0 .. 8191 (S1), so a difference is below
+// 2^13, a squared length, a dot and a cross product below 2^27, num below 2^54 and the two sides of S4, 16 num and t^2 den with
+// t <= 2^12, below 2^58 and 2^51: exact in int64.
+__device__ __forceinline__ void simplify_distance(int px, int py, int ax, int ay, int bx, int by, long long& num, long long& den) {
+    const int ux = bx - ax, uy = by - ay, vx = px - ax, vy = py - ay, wx = px - bx, wy = py - by;
+    const long long da = (long long)(vx * vx + vy * vy), db = (long long)(wx * wx + wy * wy);
+    const long long d = (long long)(ux * ux + uy * uy), dot = (long long)(vx * ux + vy * uy), cross = (long long)(ux * vy - uy * vx);
+    den = d == 0 ? 1 : d;
+    num = d == 0 ? da : (dot <= 0 ? da * d : (dot >= d ? db * d : cross * cross));
+}
+
+__device__ __forceinline__ long long cross2(int2 p, int2 q) { return (long long)(p.x * q.y - q.x * p.y); }      // below 2^27
+
+__device__ __forceinline__ long long wave_sum64(long long v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+#define SIMPLIFY_WAVES (VPU_SIMPLIFY_THREADS / 64)
+
+// -------------------------------------------------------------------------------------------------------------------
+// (1) split, form A: one workgroup per loop, any length, its positions block-strided.  A round has three steps with a barrier
+//     after each: every live position adds its num to its chain's maximum (the slot of the chain's first position i; an integer
+//     atomic maximum, exact and order-free); every live position that has the maximum offers its position to the chain's minimum;
+//     every live position reads (num, k) of its chain, applies S4 and takes its new chain, and position k clears the slot pair
+//     that the next round uses at i.  The slots are read with atomic loads: they were written by atomics, which the CU's vector
+//     L1 does not see.  The block-wide OR of the splits ends the rounds, at most n of them: a round that splits keeps a vertex.
+__global__ __launch_bounds__(VPU_SIMPLIFY_THREADS) void simplify_split_a_kernel(const int2* __restrict__ points, const int* __restrict__ offsets,
+                                                                                const int* __restrict__ item_loops, int n_items, int V,
+                                                                                int loop_max, int t, int skip_short, int32_t* __restrict__ work) {
+    __shared__ long long red[2][SIMPLIFY_WAVES];
+    __shared__ int wave_cnt[SIMPLIFY_WAVES];
+    const SimplifyWork w = simplify_work(work, V, loop_max);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = clampi(item_loops[n_items], 0, loop_max);
+    for (int l = blockIdx.x; l < L; l += gridDim.x) {
+        int a, n;
+        simplify_loop(offsets, l, V, a, n);
+        if (skip_short && n <= VPU_SIMPLIFY_SHORT) continue;          // (the same in every thread)
+        const int2* __restrict__ P = points + a;
+        int2* state = w.state + a;
+        long long* best[2] = {w.best + a, w.best + V + a};
+        int* bpos[2] = {w.bpos + a, w.bpos + V + a};
+        for (int p = tid; p < n; p += VPU_SIMPLIFY_THREADS) {
+            state[p] = p == 0 ? make_int2(-1, n) : make_int2(0, n);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                __hip_atomic_store(best[s] + p, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(bpos[s] + p, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();
+        int rounds = 0;
+        long long tt = 0;                                             // S3: the first round is S4 with t = 0
+        for (int r = 0; r <= n; ++r) {
+            long long* bst = best[r & 1];
+            int* bps = bpos[r & 1];
+            for (int p = tid; p < n; p += VPU_SIMPLIFY_THREADS) {
+                const int2 s = state[p];
+                if (s.x < 0) continue;
+                const int i = clampi(s.x, 0, n - 1), j = clampi(s.y, 1, n);
+                const int2 pp = P[p], pa = P[i], pb = P[j == n ? 0 : j];
+                long long num, den;
+                simplify_distance(pp.x, pp.y, pa.x, pa.y, pb.x, pb.y, num, den);
+                __hip_atomic_fetch_max(bst + i, num, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            for (int p = tid; p < n; p += VPU_SIMPLIFY_THREADS) {
+                const int2 s = state[p];
+                if (s.x < 0) continue;
+                const int i = clampi(s.x, 0, n - 1), j = clampi(s.y, 1, n);
+                const int2 pp = P[p], pa = P[i], pb = P[j == n ? 0 : j];
+                long long num, den;
+                simplify_distance(pp.x, pp.y, pa.x, pa.y, pb.x, pb.y, num, den);
+                if (num == __hip_atomic_load(bst + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    __hip_atomic_fetch_min(bps + i, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            int any = 0;
+            for (int p = tid; p < n; p += VPU_SIMPLIFY_THREADS) {
+                const int2 s = state[p];
+                if (s.x < 0) continue;
+                const int i = clampi(s.x, 0, n - 1), j = clampi(s.y, 1, n);
+                const int2 pa = P[i], pb = P[j == n ? 0 : j];
+                const int ux = pb.x - pa.x, uy = pb.y - pa.y;
+                const long long d = (long long)(ux * ux + uy * uy), den = d == 0 ? 1 : d;
+                const long long num = __hip_atomic_load(bst + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const int k = clampi(__hip_atomic_load(bps + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0, n - 1);
+                if (16 * num > tt * den) {                            // S4; both sides below 2^58 (simplify_distance)
+                    any = 1;
+                    if (p < k) state[p] = make_int2(i, k);
+                    else if (p > k) state[p] = make_int2(k, j);
+                    else {
+                        state[p] = make_int2(-1, j);                  // kept: its successor among the kept, and i's
+                        state[i].y = k;                               // (position i is kept: its own thread leaves it alone)
+                        __hip_atomic_store(best[(r + 1) & 1] + i, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(bpos[(r + 1) & 1] + i, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                } else {
+                    state[p] = make_int2(-2, 0);
+                }
+            }
+            if (!__syncthreads_or(any)) break;
+            ++rounds;
+            tt = (long long)t * t;
+        }
+        // the kept positions' ranks, the kept count, and twice the signed areas of the exact and of the simplified loop (S5)
+        int carry = 0;
+        long long exact = 0, simple = 0;
+        for (int base = 0; base < n; base += VPU_SIMPLIFY_THREADS) {
+            const int p = base + tid;
+            int kept = 0;
+            if (p < n) {
+                const int2 s = state[p], pp = P[p];
+                kept = s.x == -1 ? 1 : 0;
+                exact += cross2(pp, P[p + 1 < n ? p + 1 : 0]);
+                if (kept) {
+                    const int q = clampi(s.y, 1, n);
+                    simple += cross2(pp, P[q == n ? 0 : q]);
+                }
+            }
+            const unsigned long long b = __ballot(kept);
+            if (lane == 0) wave_cnt[wave] = __popcll(b);
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int v = 0; v < SIMPLIFY_WAVES; ++v) {
+                const int c = wave_cnt[v];
+                if (v < wave) before += c;
+                all += c;
+            }
+            __syncthreads();
+            if (p < n) {
+                w.rank[a + p] = kept ? carry + before + __popcll(b & ((1ull << lane) - 1ull)) : -1;
+                w.loopof[a + p] = l;
+            }
+            carry += all;
+        }
+        exact = wave_sum64(exact);
+        simple = wave_sum64(simple);
+        if (lane == 0) {
+            red[0][wave] = exact;
+            red[1][wave] = simple;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            exact = simple = 0;
+#pragma unroll
+            for (int v = 0; v < SIMPLIFY_WAVES; ++v) {
+                exact += red[0][v];
+                simple += red[1][v];
+            }
+            w.cnt[l] = carry >= 3 && simple != 0 ? carry : 0;
+            w.lhole[l] = exact < 0 ? 1 : 0;
+            w.rounds[l] = rounds;
+        }
+        __syncthreads();                                              // red and wave_cnt are free for the next loop
+    }
+}
+
+// (1) split, form B: the loops of at most 64 corners, one wave per loop, four loops per workgroup at a time.  Lane p holds P_p,
+//     the kept set is a 64-bit mask in every lane, i and j come from bit scans of it, the chain ends from two shuffles, and the
+//     chain's (num, smallest k) from a segmented inclusive scan over the lanes of equal i in six shuffle steps, read from the
+//     chain's last lane j - 1.  No LDS, no barrier.  Retired chains are worked out again every round: that costs nothing in a wave.
+__global__ __launch_bounds__(VPU_SIMPLIFY_THREADS) void simplify_split_b_kernel(const int2* __restrict__ points, const int* __restrict__ offsets,
+                                                                                const int* __restrict__ item_loops, int n_items, int V,
+                                                                                int loop_max, int t, int32_t* __restrict__ work) {
+    const SimplifyWork w = simplify_work(work, V, loop_max);
+    const int lane = threadIdx.x & 63;
+    const int L = clampi(item_loops[n_items], 0, loop_max);
+    const unsigned long long below = (1ull << lane) - 1ull, above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+    for (int l = blockIdx.x * SIMPLIFY_WAVES + (threadIdx.x >> 6); l < L; l += gridDim.x * SIMPLIFY_WAVES) {
+        int a, n;
+        simplify_loop(offsets, l, V, a, n);
+        if (n > VPU_SIMPLIFY_SHORT) continue;                         // (the same in every lane)
+        const bool in = lane < n;
+        const int2 pp = in ? points[a + lane] : make_int2(0, 0);
+        unsigned long long kept = 1ull;
+        int rounds = 0;
+        long long tt = 0;                                             // S3: the first round is S4 with t = 0
+        for (int r = 0; r <= n; ++r) {
+            const bool live = in && !((kept >> lane) & 1ull);         // (lane 0 is kept, so a live lane has a kept one below)
+            const int i = live ? 63 - __clzll((long long)(kept & below)) : -1;
+            const int j = (kept & above) ? __ffsll((long long)(kept & above)) - 1 : n;
+            const int ia = i < 0 ? 0 : i, jb = j >= n ? 0 : j;
+            const int ax = __shfl(pp.x, ia, 64), ay = __shfl(pp.y, ia, 64), bx = __shfl(pp.x, jb, 64), by = __shfl(pp.y, jb, 64);
+            long long num, den;
+            simplify_distance(pp.x, pp.y, ax, ay, bx, by, num, den);
+            long long bn = live ? num : -1;
+            int bk = lane;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const long long on = __shfl_up(bn, o, 64);
+                const int ok = __shfl_up(bk, o, 64), oi = __shfl_up(i, o, 64);
+                if (live && lane >= o && oi == i && on >= bn) {       // (>=: the lower lanes win a tie)
+                    bn = on;
+                    bk = ok;
+                }
+            }
+            const int last = clampi(j - 1, 0, 63);
+            const long long cn = __shfl(bn, last, 64);
+            const int ck = __shfl(bk, last, 64);
+            const unsigned long long add = __ballot(live && ck == lane && 16 * cn > tt * den);       // S4; below 2^58
+            if (!add) break;
+            kept |= add;
+            ++rounds;
+            tt = (long long)t * t;
+        }
+        const bool mine = in && ((kept >> lane) & 1ull);
+        const int nx = lane + 1 < n ? lane + 1 : 0;
+        const int q = (kept & above) ? __ffsll((long long)(kept & above)) - 1 : 0;
+        const int2 pn = make_int2(__shfl(pp.x, nx, 64), __shfl(pp.y, nx, 64)), pq = make_int2(__shfl(pp.x, q, 64), __shfl(pp.y, q, 64));
+        const long long exact = wave_sum64(in ? cross2(pp, pn) : 0ll), simple = wave_sum64(mine ? cross2(pp, pq) : 0ll);
+        const int count = n > 0 ? __popcll(kept) : 0;
+        if (in) {
+            w.rank[a + lane] = mine ? __popcll(kept & below) : -1;
+            w.loopof[a + lane] = l;
+        }
+        if (lane == 0) {
+            w.cnt[l] = count >= 3 && simple != 0 ? count : 0;
+            w.lhole[l] = exact < 0 ? 1 : 0;
+            w.rounds[l] = rounds;
+        }
+    }
+}
+
+// (2) offsets: ONE workgroup scans the loops' kept counts as in (2) of the trace: a surviving loop gets its index among the
+//     survivors and its first point, writes its offset and its hole flag (below loop_cap); thread 0 the closing offset and the
+//     totals {V', L', dropped, the most rounds of a loop}.
+__global__ __launch_bounds__(1024) void simplify_offsets_kernel(const int* __restrict__ item_loops, int n_items, int V, int loop_max,
+                                                                int32_t* __restrict__ work, int* __restrict__ out_offsets,
+                                                                uint8_t* __restrict__ out_hole, int loop_cap, int* __restrict__ firsts) {
+    __shared__ int wave_sum[16];
+    __shared__ int most;
+    const SimplifyWork w = simplify_work(work, V, loop_max);
+    const int tid = threadIdx.x;
+    const int L = clampi(item_loops[n_items], 0, loop_max);
+    if (tid == 0) most = 0;
+    __syncthreads();
+    int loops = 0, pts = 0, mine = 0;                                 // (loops, pts: the same values in every thread)
+    for (int off = 0; off < L; off += 4096) {
+        const int i0 = off + 4 * tid;
+        int c[4], alive[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            c[u] = i0 + u < L ? clampi(w.cnt[i0 + u], 0, V) : 0;
+            alive[u] = c[u] > 0 ? 1 : 0;
+            if (i0 + u < L) mine = max(mine, w.rounds[i0 + u]);
+        }
+        int all_loops, all_pts;
+        int at_loop = loops + block_scan(alive[0] + alive[1] + alive[2] + alive[3], wave_sum, all_loops);
+        int at_pt = pts + block_scan(c[0] + c[1] + c[2] + c[3], wave_sum, all_pts);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (i0 + u < L) {
+                w.nidx[i0 + u] = at_loop;
+                w.noff[i0 + u] = at_pt;
+                if (alive[u] && (unsigned)at_loop < (unsigned)loop_cap) {
+                    out_offsets[at_loop] = at_pt;
+                    out_hole[at_loop] = (uint8_t)(w.lhole[i0 + u] != 0);
+                }
+            }
+            at_loop += alive[u];
+            at_pt += c[u];
+        }
+        loops += all_loops;
+        pts += all_pts;
+    }
+    atomicMax(&most, mine);                                           // (LDS; after the barriers of block_scan or the one below)
+    __syncthreads();
+    if (tid == 0) {
+        w.nidx[L] = loops;
+        w.noff[L] = pts;
+        if ((unsigned)loops < (unsigned)loop_cap) out_offsets[loops] = pts;
+        int* tot = firsts + 2 * (n_items + 1);
+        tot[0] = pts;
+        tot[1] = loops;
+        tot[2] = L - loops;
+        tot[3] = most;
+    }
+}
+
+// (3) place: every kept corner of a surviving loop stores its (x, y) with one 8-byte store at offset[loop'] + rank (below cap);
+//     the first n + 1 threads write the items' first surviving loops and first points.  A corner counts only when the loop that
+//     work names for it does hold it: then this call's split wrote its rank.
+__global__ __launch_bounds__(256) void simplify_place_kernel(const int2* __restrict__ points, const int* __restrict__ offsets,
+                                                             const int* __restrict__ item_loops, int n_items, int V, int loop_max,
+                                                             const int32_t* __restrict__ work, int2* __restrict__ out_points, int cap,
+                                                             int* __restrict__ firsts) {
+    const SimplifyWork w = simplify_work(const_cast<int32_t*>(work), V, loop_max);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int L = clampi(item_loops[n_items], 0, loop_max);
+    if (i <= n_items) {
+        const int f = clampi(item_loops[i], 0, L);
+        firsts[i] = w.nidx[f];
+        firsts[n_items + 1 + i] = w.noff[f];
+    }
+    if (i >= V || L == 0) return;
+    const int l = clampi(w.loopof[i], 0, L - 1);
+    int a, n;
+    simplify_loop(offsets, l, V, a, n);
+    if (i < a || i >= a + n) return;
+    const int r = w.rank[i], c = w.cnt[l];
+    if (r < 0 || r >= c) return;
+    const int at = w.noff[l] + r;
+    if ((unsigned)at < (unsigned)cap) out_points[at] = points[i];
+}
+
+}  // namespace
+
+extern "C" int vpu_outline_simplify_batched(const int32_t* points, const int32_t* offsets, const int32_t* item_loops, int32_t n, int32_t V,
+                                            int32_t loop_max, int32_t t, int32_t short_form, int32_t* work, int64_t work_len,
+                                            int32_t* out_points, int32_t cap, int32_t* out_offsets, int32_t loop_cap, uint8_t* out_hole,
+                                            int32_t* firsts, void* stream) {
+    vpu_clear_stale_error();
+    if (!points || !offsets || !item_loops || !firsts || n < 1 || V < 0 || loop_max < 0 || cap < 0 || loop_cap < 0 ||
+        (cap > 0 && !out_points) || (loop_cap > 0 && (!out_offsets || !out_hole))) {
+        vpu_set_error("outline_simplify_batched: null points, offsets, item_loops, firsts, out_points, out_offsets or out_hole, n < 1, "
+                      "or a negative V, loop_max or cap");
+        return VPU_ERR_ARG;
+    }
+    if (t < 0 || t > 4096 || (short_form != 0 && short_form != 1)) {
+        vpu_set_error("outline_simplify_batched: t outside 0 .. 4096 quarter pixels, or short_form not 0 (form A) or 1 (form B)");
+        return VPU_ERR_ARG;
+    }
+    if (V > 0 && loop_max > 0 && (!work || work_len < VPU_SIMPLIFY_WORK_INTS(V, loop_max))) {
+        vpu_set_error("outline_simplify_batched: null work or work_len below VPU_SIMPLIFY_WORK_INTS(V, loop_max)");
+        return VPU_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(work) % 16 || reinterpret_cast<uintptr_t>(points) % 8 || reinterpret_cast<uintptr_t>(out_points) % 8 ||
+        reinterpret_cast<uintptr_t>(offsets) % 8 || reinterpret_cast<uintptr_t>(out_offsets) % 8 ||
+        reinterpret_cast<uintptr_t>(item_loops) % 4 || reinterpret_cast<uintptr_t>(firsts) % 4) {
+        vpu_set_error("outline_simplify_batched: work not 16-byte, points, out_points, offsets or out_offsets not 8-byte, or item_loops "
+                      "or firsts not 4-byte aligned");
+        return VPU_ERR_ALIGN;
+    }
+    if (V == 0 || loop_max == 0) return 0;                            // no loop anywhere: nothing to launch
+    const int2* pts = reinterpret_cast<const int2*>(points);
+    const unsigned blocks_a = (unsigned)(loop_max < 2048 ? loop_max : 2048);
+    simplify_split_a_kernel<<<blocks_a, VPU_SIMPLIFY_THREADS, 0, ST>>>(pts, offsets, item_loops, n, V, loop_max, t, short_form, work);
+    if (short_form == 1) {
+        const int64_t groups = ((int64_t)loop_max + SIMPLIFY_WAVES - 1) / SIMPLIFY_WAVES;
+        simplify_split_b_kernel<<<(unsigned)(groups < 2048 ? groups : 2048), VPU_SIMPLIFY_THREADS, 0, ST>>>(pts, offsets, item_loops, n, V,
+                                                                                                            loop_max, t, work);
+    }
+    simplify_offsets_kernel<<<1, 1024, 0, ST>>>(item_loops, n, V, loop_max, work, out_offsets, out_hole, loop_cap, firsts);
+    const int64_t threads = V > n + 1 ? V : n + 1;
+    simplify_place_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, ST>>>(pts, offsets, item_loops, n, V, loop_max, work,
+                                                                            reinterpret_cast<int2*>(out_points), cap, firsts);
+    return vpu_check_launch("vpu_outline_simplify_batched");
+}

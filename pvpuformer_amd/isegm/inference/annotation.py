@@ -30,6 +30,7 @@ import torch
 
 from .clicker import Click, Clicker
 from .outlines import DeviceOutlineOps, HostOutlineOps
+from .polygons import check_request
 from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
 from .runs import KIND_LABELS, KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map, stack_objects
 from ._batchcore import PackedLayout, host_count_box, pack_mask, unpack_mask, upload_structs
@@ -439,13 +440,16 @@ class AnnotationPool:
         self._own_readbacks += 2
         return rm
 
-    def label_outlines(self, aid, labels=None, preview=True):
+    def label_outlines(self, aid, labels=None, preview=True, tolerance=None):
         """{label: Outline} (outlines.py): the polygon loops of ``label_map(aid, preview) == label`` for every label of
         ``labels`` (integers in 0 .. 65535; default: every committed object's label and, with ``preview``, that of the object
         in progress), traced on the device from the map built as ``label_map`` builds it.  One item per label, all in ONE trace:
         two read-backs.  A label no pixel holds gives an outline without loops; without a label to trace the result is {} and
-        the device is not touched."""
+        the device is not touched.  With a ``tolerance`` in pixels (0 .. 1024; sides up to 8191, else ValueError before any
+        launch) {label: Polygons} (polygons.py): the loops simplified on the device, three read-backs."""
         a = self._ann(aid)
+        if tolerance is not None:
+            check_request(tolerance, [tuple(a.labels.shape)])
         drawn = preview and not a.empty
         if labels is None:
             labels = [r["label"] for r in a.records] + ([self._next_label(a)] if drawn else [])
@@ -459,29 +463,38 @@ class AnnotationPool:
         if drawn:
             source = a.labels.clone()
             self.ops.compose([self._item(a, labels=source, label=self._next_label(a), mode=2)], self.prob_thresh, None)
-        got = self.ops_outlines.trace([(source, KIND_LABELS, 0.0, int(label)) for label in labels])
-        self._own_readbacks += 2
+        items = [(source, KIND_LABELS, 0.0, int(label)) for label in labels]
+        got = self.ops_outlines.trace(items) if tolerance is None else self.ops_outlines.trace(items, tolerance)
+        self._own_readbacks += 2 if tolerance is None else 3
         return {int(label): outline for label, outline in zip(labels, got)}
 
-    def export(self, aid, polygons=False):
+    def export(self, aid, polygons=False, tolerance=None):
         """The finished objects in COCO's form: the records of ``objects(aid)``, each with ``segmentation = dict(size=[H, W],
         counts=[...])``, the uncompressed run-length encoding of the pixels that hold its label now (an object that later
         ones have covered keeps its record; its counts are then ``[H * W]``).  ONE encode of the committed label map, without
         the object in progress: two read-backs.  With ``polygons`` each record also carries ``polygons``, the outer loops of
         those pixels in COCO's polygon form (``Outline.to_coco()``), and ``polygon_holes``, the number of hole loops that form
-        leaves out, from ONE trace of the committed label map: two more read-backs.  [] without touching the device when no
-        object is finished."""
+        leaves out, from ONE trace of the committed label map: two more read-backs.  With ``polygons`` and a ``tolerance`` in
+        pixels the loops are simplified on the device (``Polygons.to_coco()``; three more read-backs instead of two),
+        ``polygon_holes`` counts the hole loops that survive, and each record also carries ``polygon_tolerance``, the quantised
+        tolerance, and ``polygon_dropped``, the loops that collapsed.  [] without touching the device when no object is
+        finished."""
         a = self._ann(aid)
+        if tolerance is not None:
+            check_request(tolerance, [tuple(a.labels.shape)])
         if not a.records:
             return []
         rm, = self.ops_runs.encode([(a.labels, KIND_LABELS, 0.0)])
         self._own_readbacks += 2
         out = [dict(r, segmentation=rm.to_coco(r["label"])) for r in a.records]
         if polygons:
-            outlines = self.label_outlines(aid, [r["label"] for r in a.records], preview=False)
+            outlines = self.label_outlines(aid, [r["label"] for r in a.records], preview=False, tolerance=tolerance)
             for e in out:
                 e["polygons"] = outlines[e["label"]].to_coco()
                 e["polygon_holes"] = int(outlines[e["label"]].holes().sum())
+                if tolerance is not None:
+                    e["polygon_tolerance"] = outlines[e["label"]].tolerance
+                    e["polygon_dropped"] = outlines[e["label"]].dropped
         return out
 
     def load(self, aid, objects, keep_labels=False):

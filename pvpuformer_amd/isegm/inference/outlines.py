@@ -14,11 +14,15 @@ O6  The way back: ``+1`` per North step and ``-1`` per South step at column ``x`
 ``vpu_outline_count_batched`` / ``vpu_outline_trace_batched`` (csrc/outline.hip) trace n maps of different sizes on the device;
 what crosses to the host is ``4 (n + 1)`` bytes of offsets, then 8 bytes per corner and about one word per loop, in two
 read-backs with the exact allocation between them.  ``host_outline`` is the numpy stand-in (``HostOutlineOps``), which runs on
-a CPU pool and may replace ``ops_outlines`` of a device pool."""
+a CPU pool and may replace ``ops_outlines`` of a device pool.
+
+With a ``tolerance`` (pixels) both op classes return ``Polygons`` (polygons.py): the same loops simplified by
+Douglas-Peucker on the device, after which only the kept corners cross to the host, in three read-backs."""
 import numpy as np
 import torch
 
 from ._batchcore import upload_structs
+from .polygons import Polygons, check_request, empty_polygons, host_simplify
 from .runs import KIND_LABELS, KIND_PROB
 
 EAST, SOUTH, WEST, NORTH = 0, 1, 2, 3
@@ -88,6 +92,10 @@ class Outline:
         """COCO's polygon form: a list of flat ``[x0, y0, x1, y1, ...]`` float lists, the outer loops only unless ``holes``."""
         keep = np.ones(len(self), dtype=bool) if holes else ~self.holes()
         return [loop.reshape(-1).astype(np.float64).tolist() for loop, k in zip(self.loops(), keep) if k]
+
+    def simplify(self, tolerance):
+        """Polygons (polygons.py): the loops simplified within ``tolerance`` pixels, rules S1-S6."""
+        return host_simplify(self, tolerance)
 
     def check(self):
         """ValueError unless this is what a trace can return: offsets from 0 to V increasing by at least 4, lattice points,
@@ -199,14 +207,19 @@ class DeviceOutlineOps:
     """The HIP kernels.  ``trace(items)``, items [(tensor [H, W], kind, thr, label)]: fp32 and ``M = tensor > thr`` for kind
     0, int16 storage of uint16 labels and ``M = tensor == label`` for kind 1 -> [Outline].  The descriptors go up in one pinned
     copy; the header comes back (synchronisation 1, ``4 (n + 1)`` bytes); exactly the needed entries are allocated; points,
-    offsets and loop counts come back in one copy (synchronisation 2)."""
+    offsets and loop counts come back in one copy (synchronisation 2).
+
+    ``trace(items, tolerance)`` -> [Polygons]: the traced points stay on the device, ``vpu_outline_simplify_batched`` runs on
+    them, the items' loop counts, first surviving loops, first kept points and the totals come back (synchronisation 2,
+    ``12 (n + 1) + 16`` bytes), then exactly ``8 V' + 4 (L' + 1) + L'`` bytes: kept points, offsets, hole flags (3)."""
 
     def __init__(self, device):
         from pvpuformer_amd import _lib, ops
         self._lib, self._ops, self.device = _lib, ops, torch.device(device)
 
-    def trace(self, items):
+    def trace(self, items, tolerance=None):
         n = len(items)
+        t = None if tolerance is None else check_request(tolerance, [tuple(item[0].shape) for item in items])
         if n == 0:
             return []
         rows = []
@@ -226,7 +239,9 @@ class DeviceOutlineOps:
         at = head.numpy()
         V = int(at[n])
         if V == 0:
-            return [empty_outline(size) for size in sizes]
+            return [empty_outline(size) if t is None else empty_polygons(size, t) for size in sizes]
+        if t is not None:
+            return self._simplified(n, sizes, desc, host, scratch, header, head, t)
         most = V // 4 + 1                                      # a loop has four corners or more: offsets [L + 1] fits
         work = torch.empty(self._ops.outline_work_len(V), device=self.device, dtype=torch.int32)
         out = torch.empty(2 * V + most + n + 1, device=self.device, dtype=torch.int32)
@@ -237,15 +252,47 @@ class DeviceOutlineOps:
         return [Outline(sizes[k], points[at[k]:at[k + 1]], offsets[first[k]:first[k + 1] + 1] - at[k]) for k in range(n)]
 
 
+    def _simplified(self, n, sizes, desc, host, scratch, header, head, t):
+        ops, at = self._ops, head.numpy()
+        V = int(at[n])
+        loop_max = V // 4                                      # a loop has four corners or more
+        work = torch.empty(ops.outline_work_len(V), device=self.device, dtype=torch.int32)
+        exact = torch.empty(2 * V + loop_max + 1, device=self.device, dtype=torch.int32)
+        points, offsets = exact[:2 * V].view(V, 2), exact[2 * V:]
+        meta = torch.empty(3 * (n + 1) + 4, device=self.device, dtype=torch.int32)
+        item_loops, firsts = meta[:n + 1], meta[n + 1:]
+        ops.outline_trace_batched(desc, host, n, scratch, header, head, work, points, offsets, item_loops)
+        work = torch.empty(ops.outline_simplify_work_len(V, loop_max), device=self.device, dtype=torch.int32)
+        out = torch.empty(2 * V + loop_max + 2, device=self.device, dtype=torch.int32)       # (an even count: offsets 8-byte aligned)
+        out_points, out_offsets = out[:2 * V].view(V, 2), out[2 * V:2 * V + loop_max + 1]
+        out_hole = torch.empty(loop_max + 1, device=self.device, dtype=torch.uint8)
+        ops.outline_simplify_batched(points, offsets, item_loops, n, V, loop_max, t, work, out_points, out_offsets, out_hole, firsts)
+        got = meta.cpu().numpy()                                                          # synchronisation 2
+        loops, first, start, (kept, alive, _, _) = got[:n + 1], got[n + 1:2 * n + 2], got[2 * n + 2:3 * n + 3], got[3 * n + 3:]
+        kept, alive = int(kept), int(alive)
+        packed = torch.cat((out[:2 * kept].view(torch.uint8), out_offsets[:alive + 1].view(torch.uint8), out_hole[:alive]))
+        raw = packed.cpu().numpy()                                                        # synchronisation 3: 8 V' + 4 (L' + 1) + L' bytes
+        assert raw.nbytes == 8 * kept + 4 * (alive + 1) + alive
+        pts = raw[:8 * kept].view(np.int32).reshape(kept, 2)
+        off = raw[8 * kept:8 * kept + 4 * (alive + 1)].view(np.int32)
+        hole = raw[8 * kept + 4 * (alive + 1):].astype(bool)
+        return [Polygons(sizes[k], pts[start[k]:start[k + 1]], off[first[k]:first[k + 1] + 1] - start[k], hole[first[k]:first[k + 1]],
+                         t / 4.0, (at[k + 1] - at[k], loops[k + 1] - loops[k]), (loops[k + 1] - loops[k]) - (first[k + 1] - first[k]))
+                for k in range(n)]
+
+
 class HostOutlineOps:
     """The numpy stand-in behind the same call; maps on a device are copied to the host."""
 
     def __init__(self, device=None):
         self.device = device
 
-    def trace(self, items):
+    def trace(self, items, tolerance=None):
+        if tolerance is not None:
+            check_request(tolerance, [tuple(item[0].shape) for item in items])
         out = []
         for tensor, kind, thr, label in items:
             _check_item(tensor, kind, thr, label)
-            out.append(host_outline(_binary(tensor.detach().cpu().numpy(), kind, thr, label)))
+            outline = host_outline(_binary(tensor.detach().cpu().numpy(), kind, thr, label))
+            out.append(outline if tolerance is None else host_simplify(outline, tolerance))
         return out

@@ -39,6 +39,7 @@ from ._batchcore import (PackedLayout, ZoomHost, host_count_box, host_roi_paste,
 from .batched import _load_image, _padded_slot, batchable
 from .regions import DeviceRegionOps, HostRegionOps, TidyItem, check_tidy_args, click_seeds
 from .outlines import DeviceOutlineOps, HostOutlineOps
+from .polygons import quantise
 from .runs import KIND_PROB, DeviceRunOps, HostRunOps, RunMap, as_run_map
 
 
@@ -294,18 +295,23 @@ class SessionPool(ZoomHost):
         self.readbacks += 2
         return {s.sid: rm for s, rm in zip(held, maps)}
 
-    def mask_outlines(self, sids=None):
+    def mask_outlines(self, sids=None, tolerance=None):
         """{sid: Outline} (outlines.py) of the mask ``probs(sid) > pred_thr`` of the named sessions (default: all open ones):
         its polygon loops on the pixel lattice, so ``outline.to_coco()`` is the mask in COCO's polygon form.  One trace for all
         of them: two read-backs (the offsets, then 8 bytes per corner).  A session without a prediction yet gives an outline
-        without loops; no session's state is touched."""
+        without loops; no session's state is touched.  With a ``tolerance`` in pixels (0 .. 1024; sides up to 8191, else
+        ValueError before any launch) {sid: Polygons} (polygons.py): the loops simplified on the device, three read-backs, and
+        only the kept corners cross to the host."""
+        if tolerance is not None:
+            quantise(tolerance)
         if sids is None:
             sids = [sid for sid, held in enumerate(self._slots) if held is not None]
         held = [self._session(sid) for sid in sids]
         if not held:
             return {}
-        got = self.ops_outlines.trace([(s.canvas[s.prev], KIND_PROB, self.pred_thr, 0) for s in held])
-        self.readbacks += 2
+        items = [(s.canvas[s.prev], KIND_PROB, self.pred_thr, 0) for s in held]
+        got = self.ops_outlines.trace(items) if tolerance is None else self.ops_outlines.trace(items, tolerance)
+        self.readbacks += 2 if tolerance is None else 3
         return {s.sid: outline for s, outline in zip(held, got)}
 
     def tidy(self, sids=None, min_area=0, max_hole=0, keep="all", seeds=None):

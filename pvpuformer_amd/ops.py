@@ -584,6 +584,38 @@ def outline_trace_batched(objs, host_objs, n, scratch, header, host_header, work
               ptr(work), work.numel(), ptr(points), cap, ptr(offsets), loop_cap, ptr(item_loops), _stream())
 
 
+SIMPLIFY_THREADS = 256      # VPU_SIMPLIFY_THREADS (include/vpu_hip.h): the workgroup of the split kernels
+SIMPLIFY_SHORT = 64         # VPU_SIMPLIFY_SHORT: the longest loop that form B takes, one wave per loop
+SIMPLIFY_FORM_A, SIMPLIFY_FORM_B = 0, 1
+# which split kernel serves the loops of at most SIMPLIFY_SHORT corners; both write the same bytes.  A: on the model maps the two
+# are level (the longest loop's rounds set the time) and A saves a launch (DESIGN section 19 has the numbers)
+SIMPLIFY_SHORT_FORM = SIMPLIFY_FORM_A
+
+
+def outline_simplify_work_len(corners, loop_max):
+    """VPU_SIMPLIFY_WORK_INTS: entries of the int32 work array of ``outline_simplify_batched``."""
+    return 10 * int(corners) + 5 * int(loop_max) + 8
+
+
+def outline_simplify_batched(points, offsets, item_loops, n, V, loop_max, t, work, out_points, out_offsets, out_hole, firsts,
+                             cap=None, loop_cap=None, short_form=None):
+    """Douglas-Peucker at ``t`` quarter pixels over the loops that ``outline_trace_batched`` left in ``points`` / ``offsets`` /
+    ``item_loops`` (V corners, at most ``loop_max`` loops): out_points int32 [*, 2], out_offsets int32 [*], out_hole uint8 [*]
+    below ``cap`` / ``loop_cap`` (default: all of them), firsts int32 [2 (n + 1) + 4] = each item's first surviving loop and
+    first point, then {V', L', dropped, most rounds} (vpu_outline_simplify_batched)."""
+    for a in (points, offsets, item_loops, work, out_points, out_offsets, firsts):
+        assert a.is_cuda and a.dtype == torch.int32 and a.is_contiguous()
+    assert out_hole.is_cuda and out_hole.dtype == torch.uint8 and out_hole.is_contiguous()
+    assert points.dim() == 2 and points.shape[1] == 2 and points.shape[0] >= V and out_points.dim() == 2 and out_points.shape[1] == 2
+    assert item_loops.numel() >= n + 1 and firsts.numel() >= 2 * (n + 1) + 4 and offsets.numel() >= loop_max + 1
+    cap = out_points.shape[0] if cap is None else int(cap)
+    loop_cap = min(out_offsets.numel(), out_hole.numel()) if loop_cap is None else int(loop_cap)
+    assert cap <= out_points.shape[0] and loop_cap <= out_offsets.numel() and loop_cap <= out_hole.numel()
+    form = SIMPLIFY_SHORT_FORM if short_form is None else int(short_form)
+    _lib.call("vpu_outline_simplify_batched", ptr(points), ptr(offsets), ptr(item_loops), n, V, loop_max, t, form, ptr(work),
+              work.numel(), ptr(out_points), cap, ptr(out_offsets), loop_cap, ptr(out_hole), ptr(firsts), _stream())
+
+
 TIDY_ALL, TIDY_SEEDED, TIDY_LARGEST = 0, 1, 2       # VPU_TIDY_* (include/vpu_hip.h)
 
 
